@@ -17,7 +17,13 @@ signers, all valid.  `--config c2` adds the 10% corrupted / non-canonical /
 small-order mix of configs[2].  Signatures are made on the GPU by the library's
 own deterministic signer (bit-exact with libsodium, tests/test_gpu_parity.py).
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+Usage: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+  A run without --full does what the headline needs and no more: set-up, W warm-up steps, K timed
+  steps of the headline (the whole-node leg on configs[1]'s keyed path, one authenticate_batch per
+  step; else the device-resident step), its outcomes checked against the construction, one JSON line.
+  --full adds every other leg (device-resident step and roofline beside the whole node, the other
+  path, the pipelined form, CPU baselines and libsodium parity, end-to-end legs, exchange step, tally
+  check).  --dump-outputs DIR writes what the headline's last timed step returned as DIR/<name>.npy.
   N > 1: either under torch.distributed.run (one rank per GPU, WORLD_SIZE set), or bare --
   the process then starts the N ranks itself (launch_ranks) before anything touches the GPU.
 """
@@ -115,6 +121,7 @@ from plenum_amd import roofline as RL  # noqa: E402
 from plenum_amd import synth  # noqa: E402
 
 METRIC = "Ed25519 request verifies/sec (whole node) at 1/2/4/8 MI355X vs host libsodium"
+DTYPE = "u32 (radix-2^25.5 GF(2^255-19), 64-bit MAD accumulators)"
 
 
 def parse():
@@ -174,6 +181,15 @@ def parse():
                     help="signers of the end_to_end.key_churn leg (all registered with addIdr; 0 = skip)")
     ap.add_argument("--churn-requests", type=int, default=1_000_000,
                     help="requests of the key_churn leg (4 batches, Zipf-distributed signers)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, every other leg: the device-resident step with its roofline (where the "
+                         "whole node is the headline), the other path and key windows, the pipelined form of the "
+                         "whole-node leg, the CPU baselines and libsodium parity, the end-to-end legs, the exchange "
+                         "step alone and the tally check.  Without it a run sets up, warms up, times --steps steps of "
+                         "the headline and prints its line (the legs that did not run are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step returned as DIR/<name>.npy "
+                         "(float32 / float64; rank 0)")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--force-dist", action="store_true",
                     help="run the N > 1 exchange path (process group, all-gather, all-reduce) even at N = 1")
@@ -270,10 +286,22 @@ def e2e_requests(eng, n, signers, alias_len, seed=1, spec=None, sig=None, pks=No
     sig_b58 = _hostpack.b58encode_rows(np.ascontiguousarray(sig[:n]).tobytes(), 64)
     reqs = []
     dumps, loads = json.dumps, json.loads
-    for i in range(n):
+    if wire and n:
+        # the text json.dumps gives for request i, written with one format string (base58 and [a-z0-9]
+        # values: nothing to escape); request 0 checked against json.dumps of its dict
+        idrs, dests, vk_pool, pool, base = spec["idrs"], spec["dests"], spec["vks"], spec["pool"], spec["req_id_base"]
+        alias = "" if spec["alias"] is None else ', "alias": "%s"' % spec["alias"]
+        fmt = ('{"identifier": "%s", "reqId": %d, "operation": {"type": "1", "dest": "%s", "verkey": "%s"' + alias
+               + '}, "protocolVersion": 1, "signature": "%s"}')
+        r = synth.nym_request_dict(spec, 0, signers)
+        r["signature"] = sig_b58[0]
+        assert fmt % (idrs[0], base, dests[0], vk_pool[0], sig_b58[0]) == dumps(r)
+        reqs = [loads(fmt % (idrs[i % signers], base + i, dests[i % pool], vk_pool[(i * 7) % pool], sig_b58[i]))
+                for i in range(n)]
+    for i in range(0 if wire else n):
         r = synth.nym_request_dict(spec, i, signers)
         r["signature"] = sig_b58[i]
-        reqs.append(loads(dumps(r)) if wire else r)
+        reqs.append(r)
     vks = ["~" + b58encode(bytes(pk[16:])) for pk in pks]
     return reqs, spec["idrs"], vks
 
@@ -417,7 +445,7 @@ def whole_node_sets(eng, n, pks, sks, alias_len, rank, sets=2):
     return out, idrs, vks
 
 
-def time_whole_node(eng, args, sets, idrs, vks, dist_on, dev, scan_threads):
+def time_whole_node(eng, args, sets, idrs, vks, dist_on, dev, scan_threads, full=True):
     """The headline: BASELINE's "verifies/sec (whole node)" -- the drop-in
     authenticator (GpuAuthNr over this rank's engine, the signers' NYMs
     registered with addIdr as Node.addGenesisNyms does) verifying batches of
@@ -435,7 +463,10 @@ def time_whole_node(eng, args, sets, idrs, vks, dist_on, dev, scan_threads):
     alternating chunks (sync, pipelined, sync, ... over K / 4 batches each),
     so drift over the run weighs on both alike.  Each timed chunk is bracketed
     by a barrier and torch.cuda.synchronize() and takes the max over ranks;
-    every outcome is checked after its chunk's clock."""
+    every outcome is checked after its chunk's clock.  full=False: the
+    synchronous form alone (the pipelined form is neither warmed nor timed).
+    Returns (figures, authenticator, the last timed synchronous batch's
+    result list)."""
     from plenum_amd.client_authn import GpuAuthNr
     K, W = args.steps, args.warmup
     n = len(sets[0])
@@ -450,7 +481,7 @@ def time_whole_node(eng, args, sets, idrs, vks, dist_on, dev, scan_threads):
     wants = [want[k % len(sets)] for k in range(K)]
     for k in range(max(1, W)):  # scan buffers grown, kid_map built, both staging sets touched
         a.authenticate_batch(sets[k % len(sets)])
-    for _ in a.authenticate_batches([sets[k % len(sets)] for k in range(max(2, W))]):
+    for _ in a.authenticate_batches([sets[k % len(sets)] for k in range(max(2, W))] if full else []):
         pass
 
     def clocked(fn):
@@ -509,11 +540,13 @@ def time_whole_node(eng, args, sets, idrs, vks, dist_on, dev, scan_threads):
     bad_sync = bad_pipe = 0
     for r in range(R):
         chunk, cw = order[bounds[r]:bounds[r + 1]], wants[bounds[r]:bounds[r + 1]]
-        for form in ("sync", "pipe"):
+        for form in (("sync", "pipe") if full else ("sync",)):
             s0 = a.stats.get("speculated", 0)
             el, outs = clocked(lambda: (sync_run if form == "sync" else pipe_run)(chunk))
             spec[form] += a.stats.get("speculated", 0) - s0
             bad = check(outs, cw)
+            if form == "sync":
+                last_res = outs[-1]
             del outs
             if form == "sync":
                 el_sync += el
@@ -523,14 +556,17 @@ def time_whole_node(eng, args, sets, idrs, vks, dist_on, dev, scan_threads):
                 bad_pipe += bad
     med = sorted(range(K), key=lambda k: per[k])[K // 2]
     pmed = sorted(range(len(pipe_per)), key=lambda k: pipe_per[k])[len(pipe_per) // 2] if pipe_per else None
-    out = {"pipelined": {"value": n * K / el_pipe, "ms_per_batch": el_pipe / K * 1e3, "seconds": el_pipe,
-                         "speculated_share": spec["pipe"] / (n * K),
-                         "yield_ms": {"p50": float(np.median(pipe_per)) * 1e3, "min": min(pipe_per) * 1e3,
-                                      "max": max(pipe_per) * 1e3} if pipe_per else None,
-                         "each_ms": [round(x * 1e3, 2) for x in pipe_per],
-                         "in_batch_ms": {k: (round(v, 3) if isinstance(v, float) else v)
-                                         for k, v in ((pipe_parts[pmed] if pmed is not None else None) or {}).items()},
-                         "mismatches": bad_pipe},
+    pipelined = None
+    if full:
+        pipelined = {"value": n * K / el_pipe, "ms_per_batch": el_pipe / K * 1e3, "seconds": el_pipe,
+                     "speculated_share": spec["pipe"] / (n * K),
+                     "yield_ms": {"p50": float(np.median(pipe_per)) * 1e3, "min": min(pipe_per) * 1e3,
+                                  "max": max(pipe_per) * 1e3} if pipe_per else None,
+                     "each_ms": [round(x * 1e3, 2) for x in pipe_per],
+                     "in_batch_ms": {k: (round(v, 3) if isinstance(v, float) else v)
+                                     for k, v in ((pipe_parts[pmed] if pmed is not None else None) or {}).items()},
+                     "mismatches": bad_pipe}
+    out = {"pipelined": pipelined,
            "synchronous": {"value": n * K / el_sync, "ms_per_batch": el_sync / K * 1e3, "seconds": el_sync,
                            "batch_ms": {"p50": float(np.median(per)) * 1e3, "min": min(per) * 1e3,
                                         "max": max(per) * 1e3},
@@ -544,7 +580,7 @@ def time_whole_node(eng, args, sets, idrs, vks, dist_on, dev, scan_threads):
            "scan_threads": scan_threads or "auto", "key_window": a._g.key_window,
            "keyed_items_share": a.stats["keyed_items"] / max(1, a.stats["batch_items"]),
            "genesis_addidr_and_builds_s": genesis_s}
-    return out, a
+    return out, a, last_res
 
 
 def time_bls_commit_round(eng, checks=25, reps=5):
@@ -928,7 +964,123 @@ def main():
         RL.set_base_window(eng._lib.edv_base_window())
     eng.set_pipeline(args.pipeline)
     eng.set_key_sort(args.key_sort)
+    # the headline is the whole-node leg where it runs (configs[1], keyed path), else the device-resident step
+    whole_on = args.whole_node_n > 0 and args.config == "c1" and args.path == "keyed"
+    if whole_on and not args.full:
+        bad = headline_whole_node(args, eng, world, rank, dev, dist_on, create_s)
+    else:
+        bad = all_legs(args, eng, world, rank, dev, dist_on, create_s, whole_on)
+    if dist_on:
+        dist.barrier()
+        dist.destroy_process_group()
+    eng.close()
+    if bad:
+        sys.exit(3)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy (float32 / float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def whole_node_outputs(res, idrs):
+    """What authenticate_batch returned for the last timed batch, as one array:
+    per request the index (into the registered identifiers, registration
+    order) of the identifier it returned, -1 where it returned anything else
+    (an exception object: the request was refused)."""
+    index = {idr: i for i, idr in enumerate(idrs)}
+    return {"whole_node_identifier_index": np.fromiter(
+        (index.get(r, -1) if isinstance(r, str) else -1 for r in res), dtype=np.float64, count=len(res))}
+
+
+def whole_node_leg(eng, args, pks, sks, world, rank, dev, dist_on, full):
+    """The whole-node leg on every rank: this rank's request sets built, then
+    time_whole_node; value = every rank's batches over the slowest rank's time."""
+    host0 = host_cpus()
+    budget = host0["affinity"]
+    if host0["cgroup_cpu_quota"]:
+        budget = min(budget, int(host0["cgroup_cpu_quota"]))
+    local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
+    # one node process per GPU: the host's CPU share divided between the ranks (0 = the scan's own rule:
+    # up to 16, one per 2k requests, within the affinity and the cgroup quota)
+    scan_threads = 0 if local_world == 1 else max(1, min(16, budget // local_world))
+    tw = time.perf_counter()
+    sets, idrs, vks = whole_node_sets(eng, args.whole_node_n, pks, sks, args.alias_len, rank)
+    build_s = time.perf_counter() - tw
+    whole, _wa, last_res = time_whole_node(eng, args, sets, idrs, vks, dist_on, dev, scan_threads, full=full)
+    del _wa
+    whole["requests_built_s"] = build_s
+    whole["host_cpus"] = host0
+    forms = [k for k in ("pipelined", "synchronous") if whole[k] is not None]
+    mis = sum(whole[k]["mismatches"] for k in forms)
+    if dist_on:
+        bad = torch.tensor([mis], dtype=torch.int64, device=dev)
+        dist.all_reduce(bad)
+        mis = int(bad.item())
+    whole["mismatches_all_ranks"] = mis
+    for k in forms:  # whole job: every rank's batches over the slowest rank's time
+        whole[k]["value_per_rank"] = whole[k]["value"]
+        whole[k]["value"] = whole[k]["value"] * world
+    return whole, sets, idrs, vks, last_res
+
+
+def headline_whole_node(args, eng, world, rank, dev, dist_on, create_s):
+    """A run without --full where the whole node is the headline: the signers'
+    keys, this rank's request sets, warm-up, --steps synchronous batches timed
+    and checked against the construction, the outputs written if asked for,
+    the line.  Returns the number of wrong outcomes (all ranks)."""
+    from plenum_amd.serialization import serialize_msg_for_signing
+    pks, sks = eng.seed_keypair_batch(synth.signer_seeds(args.signers))
+    whole, sets, idrs, vks, last_res = whole_node_leg(eng, args, pks, sks, world, rank, dev, dist_on, False)
+    if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, whole_node_outputs(last_res, idrs))
+        sample = sets[0][:4096]  # (one round of the dest / verkey pools)
+        mlen_mean = float(np.mean([len(serialize_msg_for_signing(r, topLevelKeysToIgnore=["signature"]))
+                                   for r in sample]))
+        # a short line (--full's holds every leg): the build's hashes without the stamp's text, the
+        # batches' p50 / min / max without each one's time
+        build = build_stamp(eng)
+        stamp = (build.get("provenance") or {}).pop("stamp", None)
+        if stamp:
+            build["provenance"]["built_at"] = stamp.get("built_at")
+        for k in ("lib", "hostpack"):  # (the paths; their sha16 stay)
+            build.pop(k, None)
+        del whole["synchronous"]["each_ms"]
+        out = {
+            "metric": METRIC, "value": whole["synchronous"]["value"], "unit": "verifies/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": whole["synchronous"]["ms_per_batch"],
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "full": False,
+            "data": "synthetic NYM requests signed on-GPU, json-encoded and decoded one by one",
+            "config": {"workload": "configs[1]: %d NYM request dicts per GPU per step, %.0f B mean signed payload, "
+                                   "%d signers (addIdr), all valid; step = one GpuAuthNr.authenticate_batch "
+                                   "(synchronous)" % (whole["requests_per_batch"], mlen_mean, args.signers),
+                       "requests_per_gpu": whole["requests_per_batch"], "signers": args.signers,
+                       "parallelism": "dp%d" % world, "path": "keyed", "base_window": RL.BASE_W},
+            "end_to_end": None, "device_resident": None, "roofline": None,
+            "engine_create_s": create_s,
+            "build": build,
+            "cpu_baseline": None,
+            "parity": {"whole_node_mismatches": whole["mismatches_all_ranks"], "ranks": world},
+            "tally": None, "collective": None,
+            "whole_node": whole,
+            "whole_node_vs_cpu": None,
+        }
+        print(json.dumps(out), flush=True)
+    return whole["mismatches_all_ranks"]
+
+
+def all_legs(args, eng, world, rank, dev, dist_on, create_s, whole_on):
+    """Every other run: the device-resident step (the headline where the whole
+    node does not run: other configs, the general path, --whole-node-n 0) and,
+    with --full, every further leg.  Returns the number of wrong outcomes."""
+    full = args.full
     n = args.n if not (args.config == "c4" and args.n == 1_000_000) else 2_000_000
+    dev_steps = args.device_steps if whole_on else args.steps  # (the headline's steps are --steps)
 
     # ---- synthetic signed batch (not timed)
     seeds = synth.signer_seeds(args.signers)
@@ -1095,7 +1247,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.device_steps):
+    for _ in range(dev_steps):
         step()  # (queued back to back: nothing in the loop waits on the device)
     torch.cuda.synchronize()
     if dist_on:
@@ -1105,7 +1257,16 @@ def main():
     # kernel phases (HIP events on the launch streams; every step is the same work): the last timed
     # step's and three more, each read after its step (untimed, so the timed loop never waits)
     phases = [eng.last_phases_ms()]
-    for _ in range(3):
+    if args.dump_outputs and rank == 0 and not whole_on:
+        # what the last timed step left: this rank's verdict per request (the accept bitmask, unpacked) and,
+        # on configs[4], the tally's counts and quorum flags
+        bits = np.unpackbits(d_words.cpu().numpy().view(np.uint8), bitorder="little")[:n]
+        outputs = {"accept": bits.astype(np.float32)}
+        if args.config == "c4":
+            outputs.update(tally_counts=d_counts.cpu().numpy().astype(np.float32),
+                           tally_quorum=d_quorum.cpu().numpy().astype(np.float32))
+        dump_outputs(args.dump_outputs, outputs)
+    for _ in range(3 if full else 0):
         step()
         phases.append(eng.last_phases_ms())
     torch.cuda.synchronize()
@@ -1114,13 +1275,13 @@ def main():
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
 
-    tally_result = tally_check() if tally_check else None
+    tally_result = tally_check() if tally_check and full else None
 
     # the exchange step alone (RCCL cost reported apart from the
     # verify): the bitmask all-gather (+ the ballot all-reduce MAX on configs[4])
     # on the same buffers, timed with events on the compute stream, max over ranks
     collective = None
-    if dist_on:
+    if dist_on and full:
         reps = 20
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         dist.barrier()
@@ -1160,7 +1321,7 @@ def main():
 
     # secondary: the other path on the same resident batch (same verdicts required)
     other = None
-    if args.general_steps > 0:
+    if full and args.general_steps > 0:
         ostep = step_general if args.path == "keyed" else step_keyed
         ostep()
         torch.cuda.synchronize()
@@ -1191,9 +1352,9 @@ def main():
             if args.config == "c1" and rank == 0:
                 other["distinct_keys"] = time_general_distinct(eng, args, n, d_msgs, d_ms, d_me, stream)
 
-    total = n * world * args.device_steps
+    total = n * world * dev_steps
     value = total / elapsed
-    ms_per_step = elapsed / args.device_steps * 1e3
+    ms_per_step = elapsed / dev_steps * 1e3
     ph = np.mean(np.array(phases), axis=0)  # per step: per-phase sums over the sub-batch launches
     launches = eng.last_launch_count()
     n_chunk = eng.last_chunk_items()  # the phase times cover the last 2^20-request chunk
@@ -1237,21 +1398,23 @@ def main():
 
     # the dominant kernel alone on the GPU (one sub-batch, no overlap), one
     # untimed step: its own roofline fraction beside the overlapped one above
-    eng.set_pipeline(1)
-    step()
-    solo = eng.last_phases_ms()
-    eng.set_pipeline(args.pipeline)
-    solo_ms = float(solo[2])
-    solo_n = eng.last_chunk_items()
-    standalone = {"avg_launch_ms": solo_ms, "n_per_launch": solo_n,
-                  "achieved": solo_n * kernel_mad / (solo_ms * 1e-3) / 1e12,
-                  "frac": solo_n * kernel_mad / (solo_ms * 1e-3) / RL.PEAK_MAD_PER_S,
-                  "note": "same kernel, one launch over the whole batch with nothing else running (untimed step)"}
+    standalone = None
+    if full:
+        eng.set_pipeline(1)
+        step()
+        solo = eng.last_phases_ms()
+        eng.set_pipeline(args.pipeline)
+        solo_ms = float(solo[2])
+        solo_n = eng.last_chunk_items()
+        standalone = {"avg_launch_ms": solo_ms, "n_per_launch": solo_n,
+                      "achieved": solo_n * kernel_mad / (solo_ms * 1e-3) / 1e12,
+                      "frac": solo_n * kernel_mad / (solo_ms * 1e-3) / RL.PEAK_MAD_PER_S,
+                      "note": "same kernel, one launch over the whole batch with nothing else running (untimed step)"}
 
     # the keyed path at the key window the drop-in authenticator picks by
     # default (client_authn KEY_STORE_BYTES / max_keys): same resident batch
     dropin = None
-    if args.dropin_steps > 0 and args.path == "keyed" and world == 1:
+    if full and args.dropin_steps > 0 and args.path == "keyed" and world == 1:
         from plenum_amd.client_authn import KEY_STORE_BYTES
         from plenum_amd.keystore import auto_window
         w_drop = auto_window(16384, KEY_STORE_BYTES)
@@ -1275,36 +1438,15 @@ def main():
 
     # ---- the headline: the whole node (GpuAuthNr over json-decoded request dicts), every rank
     whole, wn_sets, wn_idrs, wn_vks = None, None, None, None
-    if args.whole_node_n > 0 and args.config == "c1" and args.path == "keyed":
-        host0 = host_cpus()
-        budget = host0["affinity"]
-        if host0["cgroup_cpu_quota"]:
-            budget = min(budget, int(host0["cgroup_cpu_quota"]))
-        local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
-        # one node process per GPU: the host's CPU share divided between the ranks (0 = the scan's own rule:
-        # up to 16, one per 2k requests, within the affinity and the cgroup quota)
-        scan_threads = 0 if local_world == 1 else max(1, min(16, budget // local_world))
-        tw = time.perf_counter()
-        wn_sets, wn_idrs, wn_vks = whole_node_sets(eng, args.whole_node_n, pks, sks, args.alias_len, rank)
-        build_s = time.perf_counter() - tw
-        whole, _wa = time_whole_node(eng, args, wn_sets, wn_idrs, wn_vks, dist_on, dev, scan_threads)
-        del _wa
-        whole["requests_built_s"] = build_s
-        whole["host_cpus"] = host0
-        if dist_on:
-            bad = torch.tensor([whole["pipelined"]["mismatches"] + whole["synchronous"]["mismatches"]],
-                               dtype=torch.int64, device=dev)
-            dist.all_reduce(bad)
-            whole["mismatches_all_ranks"] = int(bad.item())
-        else:
-            whole["mismatches_all_ranks"] = whole["pipelined"]["mismatches"] + whole["synchronous"]["mismatches"]
-        for k in ("pipelined", "synchronous"):  # whole job: every rank's batches over the slowest rank's time
-            whole[k]["value_per_rank"] = whole[k]["value"]
-            whole[k]["value"] = whole[k]["value"] * world
+    if whole_on:
+        whole, wn_sets, wn_idrs, wn_vks, last_res = whole_node_leg(eng, args, pks, sks, world, rank, dev, dist_on, full)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, whole_node_outputs(last_res, wn_idrs))
+        del last_res
 
     cpu = None
     lib_mis = 0 if whole is None else whole["mismatches_all_ranks"]
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         s = min(args.cpu_sample if args.config != "c3" else args.cpu_sample // 4, n)
         sig_h = d_sig[:s].cpu().numpy()
         pk_h = d_pk[:s].cpu().numpy()
@@ -1340,7 +1482,7 @@ def main():
             cpu["reference_path_configs0"] = reference_path_baseline(eng, args.e2e_c0, host)
 
     e2e = None
-    if rank == 0 and world == 1 and args.config == "c1" and args.key_order == "arrival":
+    if full and rank == 0 and world == 1 and args.config == "c1" and args.key_order == "arrival":
         e2e = {}
         if args.e2e_c0 > 0:
             reqs, idrs, vks = e2e_requests(eng, args.e2e_c0, 100, 0, seed=11)
@@ -1381,11 +1523,11 @@ def main():
                     "cpu": "cpu_baseline.value: libsodium %s crypto_sign_verify_detached on %d host threads" % (
                         cpu.get("sample", "").split("libsodium ")[-1].split(" ")[0] or "1.0.18", cpu["cores"])}
     device_resident = {
-        "value": value, "unit": "verifies/s", "steps": args.device_steps, "warmup": args.warmup,
+        "value": value, "unit": "verifies/s", "steps": dev_steps, "warmup": args.warmup,
         "ms_per_step": ms_per_step, "path": args.path,
         "note": "one step = the verify kernels over this rank's %d requests already resident in HBM (hash -> comb "
                 "-> encode on the keyed path), %d steps queued back to back; the roofline is this leg's dominant "
-                "kernel" % (n, args.device_steps),
+                "kernel" % (n, dev_steps),
         "phase_ms": {"hash": float(ph[0]), "table": float(ph[1]),
                      ("comb" if args.path == "keyed" else "dsm"): dsm_sum, "encode": float(ph[3]),
                      "note": "per-phase sums over the %d sub-batch launches of the last %d-request chunk" % (
@@ -1409,7 +1551,7 @@ def main():
                         "batch; authenticate_batches (two batches in flight) beside it (whole_node.pipelined)" % (
                             whole["requests_per_batch"], mlen_mean, args.signers))
         else:
-            head_value, head_ms, head_steps = value, ms_per_step, args.device_steps
+            head_value, head_ms, head_steps = value, ms_per_step, dev_steps
             workload = "configs[%d]: %d %s per GPU, %.0f B mean signed payload, %d signers%s%s; step = the verify " \
                        "kernels over HBM-resident inputs" % (
                            int(args.config[1]), n,
@@ -1422,7 +1564,7 @@ def main():
         out = {
             "metric": METRIC, "value": head_value, "unit": "verifies/s", "n_gpus": world, "steps": head_steps,
             "warmup": args.warmup, "ms_per_step": head_ms, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u32 (radix-2^25.5 GF(2^255-19), 64-bit MAD accumulators)",
+            "vs_baseline": None, "dtype": DTYPE, "full": full,
             "data": ("synthetic NYM requests signed on-GPU (deterministic Ed25519, libsodium-exact)"
                      + (", json-encoded and decoded one by one" if whole is not None else "")),
             "config": {"workload": workload, "requests_per_gpu": (whole or {}).get("requests_per_batch", n),
@@ -1470,12 +1612,7 @@ def main():
             "whole_node_vs_cpu": whole_vs,
         }
         print(json.dumps(out), flush=True)
-    if dist_on:
-        dist.barrier()
-        dist.destroy_process_group()
-    eng.close()
-    if mismatches or lib_mis:
-        sys.exit(3)
+    return mismatches + lib_mis
 
 
 if __name__ == "__main__":

@@ -30,7 +30,7 @@ def _free_port():
 def test_bench_two_ranks_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--dist-backend", "gloo", "--same-device", "--config", "c4", "--requests", "160000",
+           "--full", "--gpus", "2", "--dist-backend", "gloo", "--same-device", "--config", "c4", "--requests", "160000",
            "--signers", "64", "--key-window", "10", "--steps", "2", "--warmup", "1", "--no-cpu",
            "--general-steps", "0", "--dropin-steps", "0", "--e2e-n", "0", "--e2e-c0", "0"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
@@ -56,7 +56,8 @@ def test_bench_gpus_2_without_launcher():
     whole-node headline ran on both ranks (each its own authenticator over its
     own json-decoded batches, the host's CPUs split between them): value =
     both ranks' requests over the slower rank's time, every outcome exact."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--same-device",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo",
+           "--same-device",
            "--requests", "131072", "--signers", "64", "--key-window", "10", "--steps", "2", "--warmup", "1",
            "--device-steps", "2", "--whole-node-n", "65536",
            "--no-cpu", "--general-steps", "0", "--dropin-steps", "0", "--e2e-n", "0", "--e2e-c0", "0"]
@@ -84,7 +85,8 @@ def test_bench_rccl_path_one_rank():
     the bitmask all-gather, the ballot all-reduce MAX on configs[4], barriers,
     the max-over-ranks timing) run as a one-rank group on this box's GPU
     (--force-dist): the calls SCALE makes at N = 2..8, exercised on ROCm."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--config", "c4", "--requests", "131072",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dist", "--config", "c4",
+           "--requests", "131072",
            "--signers", "64", "--key-window", "10", "--steps", "2", "--warmup", "1", "--no-cpu",
            "--general-steps", "0", "--dropin-steps", "0", "--e2e-n", "0", "--e2e-c0", "0"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
@@ -109,7 +111,8 @@ def test_configs4_per_gpu_shard_at_full_size():
     rule included, plenum/server/quorums.py:15-32, models.py:21-37,
     replica.py:1289-1291), and libsodium 1.0.18 agrees with the GPU on every
     one of the 2M verdicts and on a 6,000-request sample timed as the CPU leg."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--config", "c4", "--requests", "2000000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dist", "--config", "c4",
+           "--requests", "2000000",
            "--key-window", "10", "--steps", "2", "--warmup", "1", "--cpu-sample", "6000",
            "--general-steps", "0", "--dropin-steps", "0", "--e2e-n", "0", "--e2e-c0", "0", "--whole-node-n", "0"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}

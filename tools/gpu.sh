@@ -7,8 +7,8 @@
 # limit of its own and the first failing step ends the pass (its log tail is printed).  STEP:
 #   tests[:K]            pytest -m gpu, one process (K: a pytest -k expression; '+' for spaces)
 #   smoke                __graft_entry__.smoke()
-#   bench:NAME[:ARGS]    python bench.py ARGS  -> RUN/bench_NAME.log   (ARGS: ',' for spaces)
-#   prof:NAME[:ARGS]     rocprofv3 --kernel-trace --stats of bench.py ARGS -> RUN/prof_NAME/
+#   bench:NAME[:ARGS]    python bench.py --full ARGS  -> RUN/bench_NAME.log   (ARGS: ',' for spaces)
+#   prof:NAME[:ARGS]     rocprofv3 --kernel-trace --stats of bench.py --full ARGS -> RUN/prof_NAME/
 #   py:NAME:SCRIPT[:ARGS]  python SCRIPT ARGS -> RUN/NAME.log (probes under tools/)
 #   pmc                  tools/pmc_passes.sh (PMC counter passes, one counter group per run)
 # e.g. tools/gpu.sh r07a tests:drain smoke bench:c1 prof:c1:--steps,5,--no-cpu
@@ -43,13 +43,13 @@ for step in "$@"; do
       ;;
     bench)
       log=$OUT/bench_$name.log
-      timeout -k 10 900 python -u bench.py ${rest//,/ } > "$log" 2>&1 || fail "$step" $? "$log"
+      timeout -k 10 900 python -u bench.py --full ${rest//,/ } > "$log" 2>&1 || fail "$step" $? "$log"
       python tools/bench_summary.py "$log"
       ;;
     prof)
       log=$OUT/prof_$name.log
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$name" -o run \
-        -- python3 bench.py ${rest//,/ } > "$log" 2>&1 || fail "$step" $? "$log"
+        -- python3 bench.py --full ${rest//,/ } > "$log" 2>&1 || fail "$step" $? "$log"
       find "$OUT/prof_$name" -name "*kernel_stats*.csv" | sort
       ;;
     py)
