@@ -353,6 +353,35 @@ int edv_verify_spans_device(edv_ctx *ctx, const void *d_sig64, const void *d_key
                             const void *d_msg_start, const void *d_msg_end, uint64_t n, void *d_accept_words,
                             void *stream);
 
+/* ------------------------------------------------ request texts from the wire
+ * The node receives each request as one JSON text (stp_zmq/zstack.py:528-549).
+ * edv_wire_scan_kernel does authenticate()'s host steps on those bytes
+ * (plenum/server/client_authn.py:72-92: the signature and identifier checks,
+ * b58decode of the signature, serializeForSig without "signature") for the
+ * texts inside a strict subset of JSON (csrc/wire_scan.h, DESIGN.md "Wire
+ * scan"); any other text is only marked EDV_WIRE_HOST -- never an error -- and
+ * the caller decodes it itself. */
+#define EDV_WIRE_OK   0   /* scanned on the GPU */
+#define EDV_WIRE_HOST 1   /* outside the GPU grammar: the caller decodes this item itself */
+#define EDV_WIRE_NO_ID 0xffffffffu  /* edv_wire_verify key_id: no registered key, use pk32[32*i..] */
+#define EDV_WIRE_SKIP  0xfffffffeu  /* edv_wire_verify key_id: leave the bit 0 */
+
+/* Upload n request texts (item i = text[text_off[i] .. text_off[i+1]); pinned memory from
+ * edv_host_alloc is DMA'd in place) and scan them.  status[n]; idr_span[2n] = identifier start
+ * (relative to the item's text) and length, zero where status != 0.  The decoded signatures and
+ * serializations stay in HBM as the context's "wire batch" until the next edv_wire_scan. */
+int edv_wire_scan(edv_ctx *ctx, const uint8_t *text, const uint64_t *text_off, uint64_t n,
+                  uint8_t *status, uint32_t *idr_span);
+/* Verify the wire batch's status-0 items: key_id[i] = registered key id, or EDV_WIRE_NO_ID
+ * (0xffffffff) to use pk32[32*i..] on the general path; EDV_WIRE_SKIP (0xfffffffe) = leave the
+ * bit 0 (no key / the host decides).  Same verdicts as edv_verify_batch(_keyed) on the same bytes.
+ * pk32 may be NULL when no item uses it; n is the wire batch's item count. */
+int edv_wire_verify(edv_ctx *ctx, const uint32_t *key_id, const uint8_t *pk32, uint64_t n, uint8_t *accept_bits);
+/* DIAGNOSTIC: read the wire batch back -- sig64[n*64], msgs (item i at text_off[i]-text_off[0]),
+ * msg_len[n] -- so tests compare bytes, not only verdicts.  Items with status != 0 read as zero
+ * length; their sig64 and msgs bytes are unspecified. */
+int edv_wire_readback(edv_ctx *ctx, uint8_t *sig64, uint8_t *msgs, uint32_t *msg_len);
+
 /* ------------------------------------------------- signing (synthetic load) */
 
 /* crypto_sign_seed_keypair for n seeds (32 bytes each): pk32_out n*32,

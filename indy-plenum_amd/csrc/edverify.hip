@@ -16,6 +16,8 @@
 //     edv_encode_kernel<M>  M results per lane share one inversion
 //                           (batch_encode.h), byte compare with R, wave
 //                           ballot into the accept bitmask.
+//   edv_wire_scan_kernel   request texts from the wire -> decoded signatures,
+//                          identifier spans and signing bytes in HBM (wire_scan.h)
 //   edv_sign_kernel / edv_keypair_kernel   deterministic Ed25519 signer
 //   edv_tally_*          distinct-voter ballots -> counts -> quorum flags.
 #include <hip/hip_runtime.h>
@@ -44,6 +46,7 @@
 #include "fe_lanes.h"
 #include "sha256.h"
 #include "verify_core.h"
+#include "wire_scan.h"
 
 using namespace edv;
 
@@ -624,6 +627,106 @@ __global__ __launch_bounds__(kBlock) void edv_subset_gather_kernel(const uint32_
   for (int k = 0; k < 4; ++k) o[k] = s[k];
   spans_out[j] = spans[i];
   spans_out[m + j] = spans[n + i];
+}
+
+// ---- request texts from the wire (edverify.h edv_wire_scan; the lane code is wire_scan.h) --------
+// The texts lie back to back in HBM (byte b of the caller's buffer at text[b - base + kWirePad],
+// kWirePad zeroed bytes in front and 64 behind, so every 16-byte load around an item stays in the
+// allocation).  A workgroup of kWireThreads lanes owns kWireThreads consecutive items, one per
+// lane, and walks their stretch of the buffer in tiles of kWireTile bytes: the tile comes into
+// LDS with coalesced 16-byte loads, every lane whose whole item lies in it parses it from LDS and
+// writes its serialization into a second LDS tile at the same offset (a serialization is never
+// longer than its text), and the tile's finished stretch goes out to `msgs` with 16-byte stores
+// (byte stores for the ragged ends, which share their 16 bytes with a neighbouring workgroup's
+// items).  The next tile starts at the first item not yet done; an item is at most kWireMaxText
+// bytes (longer ones are marked for the host unread), so every tile finishes at least one.
+// Per item: status, the identifier span, the decoded signature, its message span in `msgs`
+// (starts[n] then ends[n], as edv_verify_spans_device takes them).
+constexpr int kWireThreads = 64;
+constexpr uint32_t kWireTile = 20 * 1024 - 64;  // in + out + 24 B = 40,856 B of LDS: four workgroups in a CU's 160 KiB
+constexpr uint64_t kWirePad = 16;
+constexpr uint64_t kWireTail = 64;
+static_assert(kWireTile % 16 == 0 && kWireTile >= kWireMaxText + 16, "a tile holds any item at any alignment");
+
+__global__ __launch_bounds__(kWireThreads) void edv_wire_scan_kernel(
+    const uint8_t* __restrict__ text, const uint64_t* __restrict__ off, uint64_t base, uint64_t first, uint64_t end,
+    uint64_t n, uint8_t* __restrict__ msgs, uint8_t* __restrict__ sig64, uint8_t* __restrict__ status,
+    uint32_t* __restrict__ idr_span, uint64_t* __restrict__ spans) {
+  __shared__ uint4 s_in[kWireTile / 16];
+  __shared__ uint4 s_out[kWireTile / 16];
+  __shared__ unsigned long long s_next, s_lo, s_hi;
+  const uint32_t tid = threadIdx.x;
+  const uint64_t i0 = first + (uint64_t)blockIdx.x * kWireThreads;
+  if (i0 >= end) return;  // (block-uniform)
+  const uint64_t i = i0 + tid;
+  const uint64_t i1 = i0 + kWireThreads < end ? i0 + kWireThreads : end;
+  const bool valid = i < i1;
+  uint64_t a = 0, b = 0;  // this lane's item in the device buffers
+  if (valid) {
+    a = off[i] - base + kWirePad;
+    b = off[i + 1] - base + kWirePad;
+  }
+  const uint64_t load_end = (off[i1] - base + kWirePad + 15) & ~15ull;  // inside the zeroed tail
+  bool done = !valid;
+  if (valid && b - a > kWireMaxText) {
+    status[i] = (uint8_t)kWireHost;
+    idr_span[2 * i] = 0;
+    idr_span[2 * i + 1] = 0;
+    spans[i] = a;
+    spans[n + i] = a;
+    done = true;
+  }
+  uint64_t t0 = (off[i0] - base + kWirePad) & ~15ull;
+  for (;;) {
+    if (tid == 0) {
+      s_next = ~0ull;
+      s_lo = ~0ull;
+      s_hi = 0;
+    }
+    for (uint32_t k = tid; k < kWireTile / 16; k += kWireThreads) {
+      const uint64_t p = t0 + 16ull * k;
+      if (p < load_end) s_in[k] = *(const uint4*)(text + p);
+    }
+    __syncthreads();
+    if (!done && b <= t0 + kWireTile) {  // (a >= t0: the tile starts at or before the first item not done)
+      const uint32_t lo = (uint32_t)(a - t0), len = (uint32_t)(b - a);
+      WireItem it;
+      const int st = wire_scan_one((const uint8_t*)s_in + lo, len, (uint8_t*)s_out + lo, it);
+      const bool ok = st == kWireOk;
+      status[i] = (uint8_t)st;
+      idr_span[2 * i] = ok ? it.idr_start : 0;
+      idr_span[2 * i + 1] = ok ? it.idr_len : 0;
+      spans[i] = a;
+      spans[n + i] = a + (ok ? it.msg_len : 0);
+      if (ok) {
+        uint4* o = (uint4*)(sig64 + 64 * i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          o[k] = make_uint4(it.sig[4 * k], it.sig[4 * k + 1], it.sig[4 * k + 2], it.sig[4 * k + 3]);
+      }
+      done = true;
+      atomicMin(&s_lo, (unsigned long long)a);
+      atomicMax(&s_hi, (unsigned long long)b);
+    }
+    if (!done) atomicMin(&s_next, (unsigned long long)a);
+    __syncthreads();
+    const uint64_t lo = s_lo, hi = s_hi, next = s_next;
+    if (lo < hi) {  // the stretch [lo, hi) of this tile's items, whole 16-byte pieces wide
+      const uint8_t* so = (const uint8_t*)s_out;
+      const uint64_t wa = (lo + 15) & ~15ull, wb = hi & ~15ull;
+      if (wa <= wb) {
+        for (uint64_t p = lo + tid; p < wa; p += kWireThreads) msgs[p] = so[p - t0];
+        for (uint64_t p = wa + 16ull * tid; p < wb; p += 16ull * kWireThreads)
+          *(uint4*)(msgs + p) = s_out[(p - t0) >> 4];
+        for (uint64_t p = wb + tid; p < hi; p += kWireThreads) msgs[p] = so[p - t0];
+      } else {
+        for (uint64_t p = lo + tid; p < hi; p += kWireThreads) msgs[p] = so[p - t0];
+      }
+    }
+    if (next == ~0ull) break;
+    __syncthreads();  // every lane has read s_next / s_lo / s_hi and s_out before the next tile resets them
+    t0 = next & ~15ull;
+  }
 }
 
 // ---- key order of the comb (edv_options.key_sort) ------------------------------
@@ -1936,6 +2039,16 @@ struct edv_ctx {
   uint64_t last_n[kSets] = {}, last_msg_base[kSets] = {};
   bool last_ok[kSets] = {};
   Buf sub_h, sub_d_in, sub_d_sig, sub_d_spans, sub_d_words, sub_h_bits;
+  // the wire batch (edv_wire_scan / edv_wire_verify / edv_wire_readback): the texts, the
+  // serializations at the same offsets, decoded signatures, message spans (starts [n] then ends
+  // [n]), status, identifier spans and text offsets in HBM; pinned staging for callers' memory
+  // that is not pinned and for the results; the status bytes kept on the host for the verify
+  Buf w_text, w_msg, w_sig, w_spans, w_status, w_idr, w_off, w_keys, w_words;
+  Buf wh_text, wh_off, wh_out, wh_keys, wh_bits;
+  uint64_t wire_n = 0, wire_bytes = 0;
+  bool wire_ok = false;
+  std::vector<uint8_t> wire_status;
+  std::vector<hipEvent_t> wire_ev;  // one per upload chunk of a scan (+ 1), made on first use
   Buf& d_stage() { return d_stage_set[cur_set]; }
 };
 
@@ -3444,6 +3557,195 @@ int edv_verify_staged_subset(edv_ctx* ctx, const uint32_t* idx, const uint8_t* p
   return 0;
 }
 
+// ---- request texts from the wire
+// items per upload + scan launch (the verify's chunks are launch_pipeline's)
+constexpr uint64_t kWireChunk = 1ull << 17;
+
+int edv_wire_scan(edv_ctx* ctx, const uint8_t* text, const uint64_t* text_off, uint64_t n, uint8_t* status,
+                  uint32_t* idr_span) {
+  int r = set_device(ctx);
+  if (r) return r;
+  ctx->wire_ok = false;
+  if (!text_off || (n && (!status || !idr_span))) return set_err(EDV_EINVAL, "null pointer");
+  if (n >= EDV_WIRE_SKIP) return set_err(EDV_EINVAL, "too many items");
+  uint64_t bad = 0;
+  for (uint64_t i = 0; i < n; ++i) bad |= (uint64_t)(text_off[i] > text_off[i + 1]);
+  if (bad) return set_err(EDV_EINVAL, "text offsets not ascending");
+  const uint64_t base = text_off[0], total = text_off[n] - base;
+  if (total && !text) return set_err(EDV_EINVAL, "null text");
+  ctx->wire_n = n;
+  ctx->wire_bytes = total;
+  ctx->wire_status.assign((size_t)n, (uint8_t)EDV_WIRE_HOST);
+  if (n == 0) {
+    ctx->wire_ok = true;
+    return 0;
+  }
+  const uint64_t bytes = kWirePad + total + kWireTail;
+  if ((r = ensure(ctx->w_text, bytes)) || (r = ensure(ctx->w_msg, bytes)) || (r = ensure(ctx->w_sig, 64 * n)) ||
+      (r = ensure(ctx->w_spans, 16 * n)) || (r = ensure(ctx->w_status, n)) || (r = ensure(ctx->w_idr, 8 * n)) ||
+      (r = ensure(ctx->w_off, 8 * (n + 1))) || (r = ensure_pinned(ctx->wh_out, 9 * n)))
+    return r;
+  const void* src_text = text + base;
+  if (total && !pinned_range(src_text, total)) {
+    if ((r = ensure_pinned(ctx->wh_text, total))) return r;
+    stage_copy(ctx->wh_text.p, src_text, total);
+    src_text = ctx->wh_text.p;
+  }
+  const void* src_off = text_off;
+  if (!pinned_range(text_off, 8 * (n + 1))) {
+    if ((r = ensure_pinned(ctx->wh_off, 8 * (n + 1)))) return r;
+    stage_copy(ctx->wh_off.p, text_off, 8 * (n + 1));
+    src_off = ctx->wh_off.p;
+  }
+  // chunks of kWireChunk items: chunk c's texts go up on stream_copy while chunk c - 1 is scanned on
+  // the context stream (a tile's 16-byte loads may touch the first bytes of the next chunk before
+  // they arrive: bytes of other items, which no lane parses)
+  hipStream_t st = ctx->stream, cs = ctx->stream_copy;
+  const uint64_t nchunks = div_up(n, kWireChunk);
+  while (ctx->wire_ev.size() < nchunks + 1) {
+    hipEvent_t ev;
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    ctx->wire_ev.push_back(ev);
+  }
+  HIP_TRY(hipEventRecord(ctx->wire_ev[nchunks], st));  // (the copies start after the work already queued)
+  HIP_TRY(hipStreamWaitEvent(cs, ctx->wire_ev[nchunks], 0));
+  uint8_t* d_text = (uint8_t*)ctx->w_text.p;
+  HIP_TRY(hipMemsetAsync(d_text, 0, kWirePad, cs));
+  HIP_TRY(hipMemsetAsync(d_text + kWirePad + total, 0, kWireTail, cs));
+  HIP_TRY(hipMemcpyAsync(ctx->w_off.p, src_off, 8 * (n + 1), hipMemcpyHostToDevice, cs));
+  for (uint64_t c0 = 0, c = 0; c0 < n; c0 += kWireChunk, ++c) {
+    const uint64_t cn = n - c0 < kWireChunk ? n - c0 : kWireChunk;
+    const uint64_t ta = text_off[c0] - base, tb = text_off[c0 + cn] - base;
+    if (tb > ta)
+      HIP_TRY(hipMemcpyAsync(d_text + kWirePad + ta, (const uint8_t*)src_text + ta, tb - ta, hipMemcpyHostToDevice,
+                             cs));
+    HIP_TRY(hipEventRecord(ctx->wire_ev[c], cs));
+    HIP_TRY(hipStreamWaitEvent(st, ctx->wire_ev[c], 0));
+    hipLaunchKernelGGL(edv_wire_scan_kernel, dim3((uint32_t)div_up(cn, kWireThreads)), dim3(kWireThreads), 0, st,
+                       (const uint8_t*)d_text, (const uint64_t*)ctx->w_off.p, base, c0, c0 + cn, n,
+                       (uint8_t*)ctx->w_msg.p, (uint8_t*)ctx->w_sig.p, (uint8_t*)ctx->w_status.p,
+                       (uint32_t*)ctx->w_idr.p, (uint64_t*)ctx->w_spans.p);
+    HIP_TRY(hipGetLastError());
+  }
+  uint8_t* h = (uint8_t*)ctx->wh_out.p;  // identifier spans, then the status bytes
+  HIP_TRY(hipMemcpyAsync(h, ctx->w_idr.p, 8 * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h + 8 * n, ctx->w_status.p, n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  memcpy(idr_span, h, 8 * n);
+  memcpy(status, h + 8 * n, n);
+  memcpy(ctx->wire_status.data(), h + 8 * n, n);
+  ctx->wire_ok = true;
+  return 0;
+}
+
+// The items idx[0 .. m) of the wire batch (status 0) on one path: their signatures and spans
+// gathered, the pipeline's kernels, bit j of the result into bit idx[j] of accept_bits.
+static int wire_verify_group(edv_ctx* ctx, bool keyed, const std::vector<uint32_t>& idx, const uint32_t* key_id,
+                             const uint8_t* pk32, uint8_t* accept_bits) {
+  const uint64_t m = idx.size(), key_bytes = keyed ? 4 : 32, nwords = div_up(m, 64), n = ctx->wire_n;
+  int r;
+  if ((r = ensure_pinned(ctx->sub_h, (key_bytes + 4) * m)) || (r = ensure(ctx->sub_d_in, (key_bytes + 4) * m)) ||
+      (r = ensure(ctx->sub_d_sig, 64 * m)) || (r = ensure(ctx->sub_d_spans, 16 * m)) ||
+      (r = ensure(ctx->sub_d_words, 8 * nwords)) || (r = ensure_pinned(ctx->sub_h_bits, 8 * nwords)))
+    return r;
+  uint8_t* h = (uint8_t*)ctx->sub_h.p;  // the keys (ids or bytes: 16-byte aligned), then the indices
+  for (uint64_t j = 0; j < m; ++j) {
+    if (keyed)
+      ((uint32_t*)h)[j] = key_id[idx[j]];
+    else
+      memcpy(h + 32 * j, pk32 + 32ull * idx[j], 32);
+  }
+  memcpy(h + key_bytes * m, idx.data(), 4 * m);
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemcpyAsync(ctx->sub_d_in.p, h, (key_bytes + 4) * m, hipMemcpyHostToDevice, st));
+  const uint8_t* d_keys = (const uint8_t*)ctx->sub_d_in.p;
+  uint64_t* d_sp = (uint64_t*)ctx->sub_d_spans.p;
+  hipLaunchKernelGGL(edv_subset_gather_kernel, dim3((uint32_t)div_up(m, kBlock)), dim3(kBlock), 0, st,
+                     (const uint32_t*)(d_keys + key_bytes * m), m, n, (const uint8_t*)ctx->w_sig.p,
+                     (const uint64_t*)ctx->w_spans.p, (uint8_t*)ctx->sub_d_sig.p, d_sp);
+  HIP_TRY(hipGetLastError());
+  set_bucketing(ctx, false);
+  r = launch_pipeline(ctx, keyed, ctx->sub_d_sig.p, d_keys, ctx->w_msg.p, d_sp, d_sp + m, m, ctx->sub_d_words.p, st);
+  if (r) return r;
+  HIP_TRY(hipMemcpyAsync(ctx->sub_h_bits.p, ctx->sub_d_words.p, 8 * nwords, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint8_t* bits = (const uint8_t*)ctx->sub_h_bits.p;
+  for (uint64_t j = 0; j < m; ++j)
+    if (bits[j >> 3] >> (j & 7) & 1) accept_bits[idx[j] >> 3] |= (uint8_t)(1u << (idx[j] & 7));
+  return 0;
+}
+
+int edv_wire_verify(edv_ctx* ctx, const uint32_t* key_id, const uint8_t* pk32, uint64_t n, uint8_t* accept_bits) {
+  int r = set_device(ctx);
+  if (r) return r;
+  if (!ctx->wire_ok) return set_err(EDV_EINVAL, "no wire batch (edv_wire_scan first)");
+  if (n != ctx->wire_n) return set_err(EDV_EINVAL, "the wire batch holds %llu items", (unsigned long long)ctx->wire_n);
+  if (n == 0) return 0;
+  if (!key_id || !accept_bits) return set_err(EDV_EINVAL, "null pointer");
+  const uint8_t* status = ctx->wire_status.data();
+  uint64_t n_keyed = 0, n_general = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const bool live = status[i] == EDV_WIRE_OK;
+    n_keyed += (uint64_t)(live && key_id[i] < EDV_WIRE_SKIP);
+    n_general += (uint64_t)(live && key_id[i] == EDV_WIRE_NO_ID);
+  }
+  if (n_general && !pk32) return set_err(EDV_EINVAL, "null pk32 with EDV_WIRE_NO_ID items");
+  if (n_keyed && ctx->key_count == 0) return set_err(EDV_EINVAL, "no registered keys");
+  memset(accept_bits, 0, (size_t)((n + 7) / 8));
+  if (n_keyed == n) {  // the steady state: every item scanned and keyed -- the batch as it lies in HBM
+    const uint64_t nwords = div_up(n, 64);
+    if ((r = ensure(ctx->w_keys, 4 * n)) || (r = ensure(ctx->w_words, 8 * nwords)) ||
+        (r = ensure_pinned(ctx->wh_bits, 8 * nwords)))
+      return r;
+    const void* src = key_id;
+    if (!pinned_range(key_id, 4 * n)) {
+      if ((r = ensure_pinned(ctx->wh_keys, 4 * n))) return r;
+      stage_copy(ctx->wh_keys.p, key_id, 4 * n);
+      src = ctx->wh_keys.p;
+    }
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(ctx->w_keys.p, src, 4 * n, hipMemcpyHostToDevice, st));
+    const uint64_t* ms = (const uint64_t*)ctx->w_spans.p;
+    set_bucketing(ctx, false);
+    r = launch_pipeline(ctx, true, ctx->w_sig.p, ctx->w_keys.p, ctx->w_msg.p, ms, ms + n, n, ctx->w_words.p, st);
+    if (r) return r;
+    HIP_TRY(hipMemcpyAsync(ctx->wh_bits.p, ctx->w_words.p, 8 * nwords, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(accept_bits, ctx->wh_bits.p, (size_t)((n + 7) / 8));
+    if (n & 7) accept_bits[n / 8] &= (uint8_t)((1u << (n & 7)) - 1);
+    return 0;
+  }
+  std::vector<uint32_t> idx;
+  for (int keyed = 1; keyed >= 0; --keyed) {  // two index-gathered launches, as edv_verify_staged_subset's
+    const uint64_t m = keyed ? n_keyed : n_general;
+    if (!m) continue;
+    idx.clear();
+    idx.reserve((size_t)m);
+    for (uint64_t i = 0; i < n; ++i)
+      if (status[i] == EDV_WIRE_OK && (keyed ? key_id[i] < EDV_WIRE_SKIP : key_id[i] == EDV_WIRE_NO_ID))
+        idx.push_back((uint32_t)i);
+    if ((r = wire_verify_group(ctx, keyed != 0, idx, key_id, pk32, accept_bits))) return r;
+  }
+  return 0;
+}
+
+int edv_wire_readback(edv_ctx* ctx, uint8_t* sig64, uint8_t* msgs, uint32_t* msg_len) {
+  int r = set_device(ctx);
+  if (r) return r;
+  if (!ctx->wire_ok) return set_err(EDV_EINVAL, "no wire batch (edv_wire_scan first)");
+  const uint64_t n = ctx->wire_n, total = ctx->wire_bytes;
+  if (n == 0) return 0;
+  if (!sig64 || !msg_len || (total && !msgs)) return set_err(EDV_EINVAL, "null pointer");
+  std::vector<uint64_t> spans((size_t)(2 * n));
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemcpyAsync(sig64, ctx->w_sig.p, 64 * n, hipMemcpyDeviceToHost, st));
+  if (total) HIP_TRY(hipMemcpyAsync(msgs, (const uint8_t*)ctx->w_msg.p + kWirePad, total, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(spans.data(), ctx->w_spans.p, 16 * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (uint64_t i = 0; i < n; ++i) msg_len[i] = (uint32_t)(spans[(size_t)(n + i)] - spans[(size_t)i]);
+  return 0;
+}
+
 int edv_verify_submit(edv_ctx* ctx, int keyed, const uint8_t* sig, int sig_format, const uint8_t* keys,
                       const uint8_t* msgs, const uint64_t* msg_off, uint64_t n, uint64_t* ticket) {
   int r = set_device(ctx);
@@ -3629,7 +3931,9 @@ void edv_destroy(edv_ctx* ctx) {
   if (ctx->stream_build) (void)hipStreamSynchronize(ctx->stream_build);
   for (edv_ctx::Buf* b : {&ctx->b_sig, &ctx->b_pk, &ctx->b_msg, &ctx->b_off, &ctx->b_bits, &ctx->b_aux, &ctx->b_build,
                           &ctx->sub_h, &ctx->sub_d_in, &ctx->sub_d_sig, &ctx->sub_d_spans, &ctx->sub_d_words,
-                          &ctx->sub_h_bits})
+                          &ctx->sub_h_bits, &ctx->w_text, &ctx->w_msg, &ctx->w_sig, &ctx->w_spans, &ctx->w_status,
+                          &ctx->w_idr, &ctx->w_off, &ctx->w_keys, &ctx->w_words, &ctx->wh_text, &ctx->wh_off,
+                          &ctx->wh_out, &ctx->wh_keys, &ctx->wh_bits})
     free_buf(*b);
   for (int k = 0; k < edv_ctx::kSets; ++k) {
     for (edv_ctx::Buf* b : {&ctx->d_stage_set[k], &ctx->d_spans[k], &ctx->s_sig[k], &ctx->s_key[k], &ctx->s_bits[k],
@@ -3639,6 +3943,7 @@ void edv_destroy(edv_ctx* ctx) {
     if (ctx->ev_sdone[k]) (void)hipEventDestroy(ctx->ev_sdone[k]);
   }
   for (edv_ctx::BuildEv& b : ctx->builds) (void)hipEventDestroy(b.ev);
+  for (hipEvent_t ev : ctx->wire_ev) (void)hipEventDestroy(ev);
   for (int k = 0; k < edv_ctx::kManyRing; ++k) {
     free_buf(ctx->h_many[k]);
     free_buf(ctx->d_many[k]);

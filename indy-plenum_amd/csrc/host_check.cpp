@@ -480,3 +480,53 @@ int edv_host_bls_verify_program(const uint8_t sig128[128], const uint8_t* msg, u
   return blsp_result_is_one(S) ? 1 : 0;
 }
 }  // extern "C"
+
+// ---- the wire scanner (wire_scan.h, the code of edv_wire_scan_kernel's lanes) on the CPU, every
+// read and write of it asserted inside the item's text / output span, for tests/test_wire_scan.py.
+#include "wire_scan.h"
+namespace {
+struct CheckedText {
+  const uint8_t* p;
+  uint32_t n;
+  uint8_t operator[](uint32_t i) const {
+    EDV_ASSERT(i < n);
+    return p[i];
+  }
+};
+struct CheckedOut {
+  uint8_t* p;
+  uint32_t n;
+  uint8_t& operator[](uint32_t i) const {
+    EDV_ASSERT(i < n);
+    return p[i];
+  }
+};
+}  // namespace
+extern "C" {
+// n texts (item i = text[off[i] .. off[i + 1])): status[n] (0 scanned, 1 the host decides),
+// idr_span[2n] (start, length; zero where status != 0), sig64[64n], msg_len[n], and item i's
+// serialization at msgs[off[i] - off[0] ..) (msgs holds off[n] - off[0] bytes).
+void hc_wire_scan(const uint8_t* text, const uint64_t* off, uint64_t n, uint8_t* status, uint32_t* idr_span,
+                  uint8_t* sig64, uint8_t* msgs, uint32_t* msg_len) {
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t len = off[i + 1] - off[i];
+    WireItem it;
+    memset(&it, 0, sizeof it);
+    int st = kWireHost;
+    if (len <= kWireMaxText) {
+      const CheckedText t{text + off[i], (uint32_t)len};
+      const CheckedOut o{msgs + (off[i] - off[0]), (uint32_t)len};
+      st = wire_scan_one(t, (uint32_t)len, o, it);
+    }
+    status[i] = (uint8_t)st;
+    const bool ok = st == kWireOk;
+    idr_span[2 * i] = ok ? it.idr_start : 0;
+    idr_span[2 * i + 1] = ok ? it.idr_len : 0;
+    msg_len[i] = ok ? it.msg_len : 0;
+    if (ok)
+      memcpy(sig64 + 64 * i, it.sig, 64);
+    else
+      memset(sig64 + 64 * i, 0, 64);
+  }
+}
+}  // extern "C"

@@ -3653,7 +3653,177 @@ PyObject* py_distinct_sm(PyObject*, PyObject* args) {
   return r;
 }
 
+// ---- the wire path (authenticate_wire_batch): the host's share is a memcpy and the batch's
+// distinct identifiers.
+//
+// gather_texts(texts, out, threads=0) -> offsets (bytes, uint64 LE, n + 1, from 0) with the n
+// bytes objects of the list copied back to back into the writable buffer `out` (the engine's
+// pinned memory) on the scan's worker pool -- a b"".join of 1M texts alone costs more than the
+// dict scan this path replaces.  None: not a list, an entry that is not exactly bytes, or out
+// too small (nothing the caller can use was written).
+PyObject* py_gather_texts(PyObject*, PyObject* args) {
+  PyObject* list;
+  Py_buffer bo;
+  int threads = 0;
+  if (!PyArg_ParseTuple(args, "Ow*|i", &list, &bo, &threads)) return nullptr;
+  struct Rel {
+    Py_buffer* a;
+    ~Rel() { PyBuffer_Release(a); }
+  } rel{&bo};
+  if (!PyList_CheckExact(list)) Py_RETURN_NONE;
+  const Py_ssize_t n = PyList_GET_SIZE(list);
+  PyObject** items = ((PyListObject*)list)->ob_item;
+  constexpr Py_ssize_t kChunk = 4096;
+  const Py_ssize_t nchunks = (n + kChunk - 1) / kChunk;
+  std::vector<uint64_t> chunk_at((size_t)nchunks + 1, 0);
+  std::atomic<int> bad{0};
+  const int t = scan_threads(n, threads);
+  run_chunks(n, t, [&](int, Py_ssize_t a, Py_ssize_t b) {
+    uint64_t sum = 0;
+    for (Py_ssize_t i = a; i < b; ++i) {
+      if (i + 8 < b) pf(items[i + 8]);
+      if (!PyBytes_CheckExact(items[i])) {
+        bad = 1;
+        return;
+      }
+      sum += (uint64_t)PyBytes_GET_SIZE(items[i]);
+    }
+    chunk_at[(size_t)(a / kChunk) + 1] = sum;
+  }, kChunk);
+  if (bad) Py_RETURN_NONE;
+  for (Py_ssize_t c = 0; c < nchunks; ++c) chunk_at[(size_t)c + 1] += chunk_at[(size_t)c];
+  if (chunk_at[(size_t)nchunks] > (uint64_t)bo.len) Py_RETURN_NONE;
+  PyObject* ret = PyBytes_FromStringAndSize(nullptr, (n + 1) * 8);
+  if (!ret) return nullptr;
+  uint64_t* off = (uint64_t*)PyBytes_AS_STRING(ret);
+  char* dst = (char*)bo.buf;
+  off[n] = chunk_at[(size_t)nchunks];
+  run_chunks(n, t, [&](int, Py_ssize_t a, Py_ssize_t b) {
+    uint64_t at = chunk_at[(size_t)(a / kChunk)];
+    for (Py_ssize_t i = a; i < b; ++i) {
+      if (i + 8 < b) pf(items[i + 8]);
+      const Py_ssize_t len = PyBytes_GET_SIZE(items[i]);
+      off[i] = at;
+      memcpy(dst + at, PyBytes_AS_STRING(items[i]), (size_t)len);
+      at += (uint64_t)len;
+    }
+  }, kChunk);
+  return ret;
+}
+
+// wire_idents(text, off_u64, status_u8, span_u32) -> (uidx, uniq): the distinct identifiers of
+// the scanned items (status 0; identifier = text[off[i] + span[2i] ..][: span[2i + 1]], ASCII by
+// the scanner's grammar) as str in first-occurrence order, and per item its index into them
+// (uint32 LE; len(uniq) for the items the host decides).  Per chunk of items on the worker
+// pool, the chunks' lists merged in order.
+PyObject* py_wire_idents(PyObject*, PyObject* args) {
+  Py_buffer bt, bf, bs, bp;
+  int threads = 0;
+  if (!PyArg_ParseTuple(args, "y*y*y*y*|i", &bt, &bf, &bs, &bp, &threads)) return nullptr;
+  struct Rel {
+    Py_buffer *a, *b, *c, *d;
+    ~Rel() {
+      PyBuffer_Release(a);
+      PyBuffer_Release(b);
+      PyBuffer_Release(c);
+      PyBuffer_Release(d);
+    }
+  } rel{&bt, &bf, &bs, &bp};
+  const Py_ssize_t n = bs.len;
+  if (bf.len != (n + 1) * 8 || bp.len != n * 8) {
+    PyErr_SetString(PyExc_ValueError, "wire_idents: offsets / status / spans mismatch");
+    return nullptr;
+  }
+  const char* text = (const char*)bt.buf;
+  const uint64_t* off = (const uint64_t*)bf.buf;
+  const uint8_t* status = (const uint8_t*)bs.buf;
+  const uint32_t* span = (const uint32_t*)bp.buf;
+  constexpr Py_ssize_t kChunk = 16384;
+  const Py_ssize_t nchunks = (n + kChunk - 1) / kChunk;
+  std::vector<std::vector<std::string_view>> local((size_t)nchunks);
+  PyObject* uidx_o = PyBytes_FromStringAndSize(nullptr, n * 4);
+  if (!uidx_o) return nullptr;
+  uint32_t* uidx = (uint32_t*)PyBytes_AS_STRING(uidx_o);
+  constexpr uint32_t kNone = 0xffffffffu;
+  const int t = scan_threads(n, threads);
+  std::atomic<int> bad{0};
+  run_chunks(n, t, [&](int, Py_ssize_t a, Py_ssize_t b) {
+    std::unordered_map<std::string_view, uint32_t> seen;
+    std::vector<std::string_view>& mine = local[(size_t)(a / kChunk)];
+    for (Py_ssize_t i = a; i < b; ++i) {
+      // every item inside the text, every span inside its item
+      if (!(off[i] <= off[i + 1] && off[i + 1] <= (uint64_t)bt.len &&
+            (status[i] != 0 || (uint64_t)span[2 * i] + span[2 * i + 1] <= off[i + 1] - off[i]))) {
+        bad = 1;
+        return;
+      }
+      // (each identifier is a line of its own in a buffer far larger than the caches: fetched ahead;
+      // the address is only a hint, checked for item i + 16 when its turn comes)
+      if (i + 16 < b) pf((const void*)((uintptr_t)text + off[i + 16] + span[2 * (i + 16)]));
+      if (status[i] != 0) {
+        uidx[i] = kNone;
+        continue;
+      }
+      const std::string_view s(text + off[i] + span[2 * i], span[2 * i + 1]);
+      auto it = seen.find(s);
+      if (it == seen.end()) {
+        it = seen.emplace(s, (uint32_t)mine.size()).first;
+        mine.push_back(s);
+      }
+      uidx[i] = it->second;  // (chunk-local until the merge)
+    }
+  }, kChunk);
+  if (bad) {
+    Py_DECREF(uidx_o);
+    PyErr_SetString(PyExc_ValueError, "wire_idents: a span outside its text");
+    return nullptr;
+  }
+  std::unordered_map<std::string_view, uint32_t> all;
+  std::vector<std::string_view> order;
+  std::vector<std::vector<uint32_t>> to_global((size_t)nchunks);
+  for (Py_ssize_t c = 0; c < nchunks; ++c) {
+    to_global[(size_t)c].reserve(local[(size_t)c].size());
+    for (const std::string_view& s : local[(size_t)c]) {
+      auto it = all.find(s);
+      if (it == all.end()) {
+        it = all.emplace(s, (uint32_t)order.size()).first;
+        order.push_back(s);
+      }
+      to_global[(size_t)c].push_back(it->second);
+    }
+  }
+  const uint32_t nu = (uint32_t)order.size();
+  run_chunks(n, t, [&](int, Py_ssize_t a, Py_ssize_t b) {
+    const std::vector<uint32_t>& map = to_global[(size_t)(a / kChunk)];
+    for (Py_ssize_t i = a; i < b; ++i) uidx[i] = uidx[i] == kNone ? nu : map[uidx[i]];
+  }, kChunk);
+  PyObject* uniq = PyList_New((Py_ssize_t)nu);
+  if (!uniq) {
+    Py_DECREF(uidx_o);
+    return nullptr;
+  }
+  for (uint32_t j = 0; j < nu; ++j) {
+    PyObject* s = PyUnicode_DecodeASCII(order[j].data(), (Py_ssize_t)order[j].size(), nullptr);
+    if (!s) {
+      Py_DECREF(uidx_o);
+      Py_DECREF(uniq);
+      return nullptr;
+    }
+    PyList_SET_ITEM(uniq, (Py_ssize_t)j, s);
+  }
+  PyObject* r = PyTuple_Pack(2, uidx_o, uniq);
+  Py_DECREF(uidx_o);
+  Py_DECREF(uniq);
+  return r;
+}
+
 PyMethodDef kMethods[] = {
+    {"gather_texts", py_gather_texts, METH_VARARGS,
+     "gather_texts(texts, out, threads=0) -> offsets (uint64 LE, n + 1) with the list's bytes copied back to back "
+     "into the writable buffer out, or None (not a list of bytes, or out too small)"},
+    {"wire_idents", py_wire_idents, METH_VARARGS,
+     "wire_idents(text, off_u64, status_u8, span_u32, threads=0) -> (uidx_u32, uniq): the distinct identifiers of "
+     "the wire-scanned items, first occurrence first; uidx = len(uniq) where status != 0"},
     {"scan_batch", py_scan_batch, METH_VARARGS,
      "scan_batch(msgs, ignore, threads=0, out=None) -> (fast, idrs, sig64, msgbuf, off, short): authenticate()'s "
      "host steps for a batch.  out = [bytearray, bytearray]: sig64 / msgbuf are written into them (grown, never "

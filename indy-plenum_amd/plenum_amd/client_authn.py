@@ -93,6 +93,11 @@ try:  # the node's per-message path: authenticate()'s host steps in one call; th
 except ImportError:  # pragma: no cover
     _authn_key = _distinct_sm = None
 
+try:  # the wire path's host share: the texts into one pinned buffer, the batch's distinct identifiers
+    from ._hostpack import gather_texts as _gather_texts, wire_idents as _wire_idents
+except ImportError:  # pragma: no cover
+    _gather_texts = _wire_idents = None
+
 try:  # native packing (csrc/hostpack.cpp)
     from ._hostpack import pack_sm as _pack_sm, pack_split64 as _pack_split64
 except ImportError:  # pragma: no cover - same layout in Python
@@ -333,7 +338,9 @@ class _GpuState:
         self.kid_map_version = None
         self.kid_map_max = 1 << 20
         self.stats = {"batches": 0, "batch_items": 0, "cache_hits": 0, "single_verifies": 0, "keyed_items": 0,
-                      "keys_registered": 0, "prefetched": 0}
+                      "keys_registered": 0, "prefetched": 0, "wire_items": 0, "wire_host_items": 0}
+        self.wire_bytes_per_item = 400.0  # sizes the next wire batch's pinned text buffer
+        self.last_wire_breakdown = None  # the last wire batch's phases (ms)
 
 
 class GpuAuthMixin:
@@ -1567,6 +1574,187 @@ class GpuAuthMixin:
             self._count_verified_keys(list(per_key), list(per_key.values()))
         return ok
 
+    # -- request texts from the wire ------------------------------------------------
+    def authenticate_wire_batch(self, texts):
+        """authenticate_batch for requests still in their wire form: texts is a
+        list of bytes, each one JSON text as the node received it (zstack.py
+        rxMsgs, before deserializeMsg).  Returns, element-wise, what
+        authenticate_batch([json.loads(t) for t in texts]) returns -- the
+        identifier, or the exception instance (same class, args and __cause__
+        class) -- and, for a text json.loads rejects, that ValueError /
+        UnicodeDecodeError instance at its position.
+
+        The host only copies the texts into pinned memory; the GPU tokenises
+        them, checks signature and identifier, base58-decodes the signature and
+        builds the signing bytes (edv_wire_scan), and the verify kernels read
+        all of it from HBM.  getVerkey is called once per distinct identifier
+        of the scanned items, in first-occurrence order.  Texts outside the GPU
+        grammar (floats, non-ASCII, \\u escapes, ... -- csrc/wire_scan.h), and
+        items whose key is not 32 bytes, are decoded here and go through
+        authenticate_batch in one call.  An engine without the wire path (a
+        MultiEngine, a test double) or a subclass with its own _prepare /
+        serializeForSig decodes the whole batch.
+
+        The wire path neither consults nor fills the verify-ahead verdict cache
+        (it is keyed by sig || ser bytes on the host, which this path never
+        materialises there)."""
+        was = gc.isenabled()
+        gc.disable()
+        try:
+            eng = self._engine()
+            if (_gather_texts is not None and _wire_idents is not None and self._native_host_steps()
+                    and getattr(eng, "supports_wire", False) and texts.__class__ is list):
+                res = self._authenticate_wire(texts, eng)
+                if res is not None:
+                    return res
+            return self._wire_decoded(texts, range(len(texts)), [None] * len(texts))
+        finally:
+            if was:
+                gc.enable()
+
+    def _wire_decoded(self, texts, where, results):
+        """results[i] for i in where, the host's way: json.loads, then one
+        authenticate_batch over the decoded ones."""
+        import json
+        idx, decoded = [], []
+        for i in where:
+            try:
+                decoded.append(json.loads(texts[i]))
+                idx.append(i)
+            except (ValueError, RecursionError) as ex:  # (JSONDecodeError and UnicodeDecodeError are ValueErrors)
+                results[i] = ex
+        if decoded:
+            for i, r in zip(idx, self.authenticate_batch(decoded)):
+                results[i] = r
+        self._g.stats["wire_host_items"] += len(where)
+        return results
+
+    def _wire_text_buffer(self, eng, nbytes):
+        buf = self._pinned(eng, "wire_text", nbytes)
+        if buf is None:
+            buf = self._g.__dict__.get("wire_text_plain")
+            if buf is None or len(buf) < nbytes:
+                buf = self._g.__dict__["wire_text_plain"] = bytearray(int(nbytes * 1.25) + 4096)
+        return buf
+
+    def _authenticate_wire(self, texts, eng):
+        """The wire batch on the GPU; None when texts is not a list of bytes."""
+        import numpy as np
+        g = self._g
+        n = len(texts)
+        if n == 0:
+            return []
+        with _engine_lock(eng):
+            t0 = _perf_counter()
+            buf = self._wire_text_buffer(eng, int(n * g.wire_bytes_per_item) + 4096)
+            off_b = _gather_texts(texts, buf, g.scan_threads)
+            if off_b is None:  # the estimate was short, or an entry is not bytes
+                if not all(t.__class__ is bytes for t in texts):
+                    return None
+                buf = self._wire_text_buffer(eng, sum(map(len, texts)))
+                off_b = _gather_texts(texts, buf, g.scan_threads)
+                if off_b is None:
+                    return None
+            off = np.frombuffer(off_b, np.uint64)
+            g.wire_bytes_per_item = max(g.wire_bytes_per_item * 0.5, int(off[-1]) / n * 1.1)
+            t1 = _perf_counter()
+            status, span = eng.wire_scan(np.frombuffer(buf, np.uint8), off)
+            t2 = _perf_counter()
+            uidx_b, uniq = _wire_idents(buf, off_b, status, span, g.scan_threads)
+            uidx = np.frombuffer(uidx_b, np.uint32)
+            nu = len(uniq)
+            ukeys = self._keys_for(uniq)  # authenticate():93-99, once per identifier
+            # per distinct identifier (one more for the items the scan left to the host): 0 = a
+            # 32-byte key (verified), 1 = no key (the verify fails), 2 = exception, 3 = the host decides
+            cls_u = np.full(nu + 1, 3, np.uint8)
+            kid_u = np.full(nu + 1, eng.WIRE_SKIP, np.uint32)
+            keys32 = []
+            for j, k in enumerate(ukeys):
+                if k.__class__ is bytes:
+                    if len(k) == 32:
+                        cls_u[j] = 0
+                        keys32.append(k)
+                    elif not k:
+                        cls_u[j] = 1
+                elif k is None:
+                    cls_u[j] = 1
+                elif isinstance(k, Exception):
+                    cls_u[j] = 2
+            id_of = {}
+            ks = self._key_store()
+            if ks is not None and keys32:
+                uniq_keys = list(dict.fromkeys(keys32))
+                self._register_waiting(ks, uniq_keys)
+                id_of = {k: i for k, i in zip(uniq_keys, ks.lookup(uniq_keys)) if i is not None}
+            general_u = []
+            for j in np.flatnonzero(cls_u[:nu] == 0).tolist():
+                i = id_of.get(ukeys[j])
+                if i is None:
+                    general_u.append(j)
+                    kid_u[j] = eng.WIRE_NO_ID
+                else:
+                    kid_u[j] = i
+            # (one native pass: numpy's fancy indexing widens the index array to intp first)
+            key_id = np.frombuffer(_gather_u32(kid_u.tobytes(), uidx_b), np.uint32) if _gather_u32 is not None \
+                else kid_u[uidx]
+            pk32 = None
+            if general_u:
+                pk_u = np.zeros((nu + 1, 32), np.uint8)
+                pk_u[general_u] = np.frombuffer(b"".join(ukeys[j] for j in general_u), np.uint8).reshape(-1, 32)
+                pk32 = pk_u[uidx]
+            if not general_u and not status.any() and not cls_u[:nu].any():
+                # every text scanned, every identifier's key registered (the node's steady state):
+                # no per-item class array
+                t3 = _perf_counter()
+                ok = eng.wire_verify(key_id, None)
+                t4 = _perf_counter()
+                g.stats["batches"] += 1
+                g.stats["batch_items"] += n
+                g.stats["keyed_items"] += n
+                g.stats["wire_items"] += n
+                failed = np.flatnonzero(~ok)
+                fails = _invalid_signatures(len(failed))
+                results = _results_from(ok.view(np.uint8).tobytes(), uidx_b, uniq)
+                for i, e in zip(failed.tolist(), fails):
+                    results[i] = e
+                t5 = _perf_counter()
+                g.last_wire_breakdown = {"gather": (t1 - t0) * 1e3, "scan": (t2 - t1) * 1e3, "keys": (t3 - t2) * 1e3,
+                                         "verify": (t4 - t3) * 1e3, "results": (t5 - t4) * 1e3,
+                                         "items": n, "host_items": 0}
+                return results
+            icls = cls_u[uidx]
+            t3 = _perf_counter()
+            n_verify = int(np.count_nonzero(icls == 0))
+            ok = eng.wire_verify(key_id, pk32) if n_verify else np.zeros(n, bool)
+            t4 = _perf_counter()
+            if n_verify:
+                g.stats["batches"] += 1
+                g.stats["batch_items"] += n_verify
+                g.stats["keyed_items"] += int(np.count_nonzero(key_id < eng.WIRE_SKIP))
+            if general_u:  # general-path keys earn a slot by verified requests
+                verified_u = np.bincount(uidx[ok], minlength=nu + 1)
+                per_key = {}
+                for j in general_u:
+                    if verified_u[j]:
+                        per_key[ukeys[j]] = per_key.get(ukeys[j], 0) + int(verified_u[j])
+                self._count_verified_keys(list(per_key), list(per_key.values()))
+            failed = np.flatnonzero((icls <= 1) & ~ok)
+            fails = _invalid_signatures(len(failed))
+            results = _results_from(ok.view(np.uint8).tobytes(), uidx_b, uniq)  # the identifier where verified
+            for i, e in zip(failed.tolist(), fails):
+                results[i] = e
+            for i in np.flatnonzero(icls == 2).tolist():
+                results[i] = self._fresh(ukeys[uidx[i]])
+            host = np.flatnonzero(icls == 3).tolist()
+            g.stats["wire_items"] += n - len(host)
+            if host:
+                self._wire_decoded(texts, host, results)
+            t5 = _perf_counter()
+            g.last_wire_breakdown = {"gather": (t1 - t0) * 1e3, "scan": (t2 - t1) * 1e3, "keys": (t3 - t2) * 1e3,
+                                     "verify": (t4 - t3) * 1e3, "results": (t5 - t4) * 1e3,
+                                     "items": n, "host_items": len(host)}
+            return results
+
     def _authenticate_batch_each(self, msgs, identifiers=None, signatures=None):
         n = len(msgs)
         identifiers = identifiers or [None] * n
@@ -1834,3 +2022,8 @@ class ReqAuthenticator:
         for a in self._authenticators:
             if hasattr(a, "prefetch"):
                 a.prefetch(reqs)
+
+    def authenticate_wire_batch(self, texts):
+        """The core authenticator's verdicts for a batch of request texts as they
+        came off the wire (GpuAuthMixin.authenticate_wire_batch)."""
+        return self.core_authenticator.authenticate_wire_batch(texts)

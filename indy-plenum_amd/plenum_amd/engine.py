@@ -311,6 +311,60 @@ class EdVerifyEngine:
             check(self._lib.edv_verify_staged_subset(self._ctx, _ptr(idx), _ptr(pk32), m, _ptr(bits)))
         return unpack_bits(bits, m)
 
+    # ------------------------------------------------ request texts from the wire
+    supports_wire = True
+    WIRE_NO_ID = 0xFFFFFFFF  # edverify.h EDV_WIRE_NO_ID: the item's key is in pk32
+    WIRE_SKIP = 0xFFFFFFFE   # edverify.h EDV_WIRE_SKIP: leave the item's bit 0
+
+    def wire_scan(self, text, text_off):
+        """Upload n request texts (item i = text[text_off[i] : text_off[i + 1]];
+        host_alloc memory is DMA'd in place) and scan them on the GPU
+        (edv_wire_scan): (status uint8[n] -- 0 scanned, 1 the caller decodes
+        the item itself --, idr_span uint32[n, 2] -- the identifier's start
+        inside the item's text and its length).  The decoded signatures and the
+        serializations stay in HBM for wire_verify / wire_readback until the
+        next wire_scan."""
+        text = text if isinstance(text, np.ndarray) and text.dtype == np.uint8 else np.frombuffer(text, np.uint8)
+        text_off = np.ascontiguousarray(text_off, dtype=np.uint64)
+        n = text_off.shape[0] - 1
+        if n < 0:
+            raise ValueError("text_off needs n + 1 entries")
+        if int(text_off[-1]) > text.shape[0]:
+            raise ValueError("text_off exceeds the text buffer")
+        status = np.ones(n, np.uint8)
+        span = np.zeros((n, 2), np.uint32)
+        check(self._lib.edv_wire_scan(self._ctx, _ptr(text) if text.size else None, _ptr(text_off), n,
+                                      _ptr(status) if n else None, _ptr(span) if n else None))
+        self._wire_shape = (n, int(text_off[-1] - text_off[0]))
+        return status, span
+
+    def wire_verify(self, key_id, pk32=None):
+        """Verdicts (bool[n]) of the wire batch's scanned items (edv_wire_verify):
+        key_id[i] = a registered key id, WIRE_NO_ID to verify with pk32[i] on
+        the general path, or WIRE_SKIP (and every item with status != 0) False."""
+        key_id = np.ascontiguousarray(key_id, dtype=np.uint32)
+        n = key_id.shape[0]
+        if pk32 is not None:
+            pk32 = _u8(pk32, 32)
+            if pk32.shape[0] != n:
+                raise ValueError("shape mismatch: key ids %d, keys %d" % (n, pk32.shape[0]))
+        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
+        check(self._lib.edv_wire_verify(self._ctx, _ptr(key_id) if n else None, _ptr(pk32), n,
+                                        _ptr(bits) if n else None))
+        return unpack_bits(bits, n)
+
+    def wire_readback(self):
+        """DIAGNOSTIC (edv_wire_readback): the wire batch's (sig64 uint8[n, 64],
+        msgs uint8[text bytes] -- item i's serialization at text_off[i] -
+        text_off[0] --, msg_len uint32[n])."""
+        n, total = getattr(self, "_wire_shape", (0, 0))
+        sig = np.zeros((n, 64), np.uint8)
+        msgs = np.zeros(total, np.uint8)
+        mlen = np.zeros(n, np.uint32)
+        check(self._lib.edv_wire_readback(self._ctx, _ptr(sig) if n else None, _ptr(msgs) if total else None,
+                                          _ptr(mlen) if n else None))
+        return sig, msgs, mlen
+
     def host_alloc(self, nbytes):
         """nbytes of pinned host memory (edv_host_alloc) as a writable ctypes
         array; host-pointer verifies copy inputs inside it to the device with no

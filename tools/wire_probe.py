@@ -1,0 +1,129 @@
+"""From the wire to a verdict, three ways, alternating in one process on one GPU:
+  (a) authenticate_wire_batch(texts)   the request texts as received; scanned on the GPU
+  (b) authenticate_batch(dicts)        the headline path over already-decoded dicts
+  (c) json.loads per text + (b)        what a node pays today from the same texts
+over configs[1]'s shape: n NYM requests (1M), 1,000 registered signers, rendered once to
+wire texts.  Every timed batch's verdicts are checked for equality between the paths, and
+the wire path must leave no item to the host.  Prints one JSON line: the three rates, the
+p50 ms per batch, and the wire path's breakdown (gather, PCIe + scan kernel, key
+resolution, verify, result list).
+
+usage: python tools/wire_probe.py [--n 1000000] [--signers 1000] [--batches 10] [--out FILE]
+       python tools/wire_probe.py --write-corpus FILE   (no GPU: the test corpus, length-prefixed,
+                                                         for indy-plenum_amd/build/wire_corpus_check)
+"""
+import argparse
+import json
+import os
+import statistics
+import struct
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "indy-plenum_amd"))
+
+
+def write_corpus(path):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import wire_model
+    texts = wire_model.corpus()
+    with open(path, "wb") as f:
+        for t in texts:
+            f.write(struct.pack("<I", len(t)))
+            f.write(t)
+    print("wrote %d texts to %s" % (len(texts), path))
+
+
+def build(eng, n, signers, alias_len):
+    """(texts, dicts, identifiers, verkeys): configs[1] NYM requests signed on the GPU."""
+    import numpy as np
+    from plenum_amd import _hostpack, pack_messages, synth
+    from plenum_amd.base58 import b58encode
+    pks, sks = eng.seed_keypair_batch(synth.signer_seeds(signers))
+    msgs, kidx, spec = synth.nym_messages(n, pks, alias_len=alias_len, seed=1)
+    buf, off = pack_messages(msgs)
+    sig = eng.sign_batch(sks, kidx, buf, off)
+    sig_b58 = _hostpack.b58encode_rows(np.ascontiguousarray(sig).tobytes(), 64)
+    idrs, dests, vk_pool, pool, base = spec["idrs"], spec["dests"], spec["vks"], spec["pool"], spec["req_id_base"]
+    alias = "" if spec["alias"] is None else ', "alias": "%s"' % spec["alias"]
+    fmt = ('{"identifier": "%s", "reqId": %d, "operation": {"type": "1", "dest": "%s", "verkey": "%s"' + alias
+           + '}, "protocolVersion": 1, "signature": "%s"}')
+    first = synth.nym_request_dict(spec, 0, signers)
+    first["signature"] = sig_b58[0]
+    assert fmt % (idrs[0], base, dests[0], vk_pool[0], sig_b58[0]) == json.dumps(first)
+    texts = [(fmt % (idrs[i % signers], base + i, dests[i % pool], vk_pool[(i * 7) % pool], sig_b58[i])).encode()
+             for i in range(n)]
+    dicts = [json.loads(t) for t in texts]
+    return texts, dicts, idrs, ["~" + b58encode(bytes(pk[16:])) for pk in pks]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--signers", type=int, default=1000)
+    ap.add_argument("--alias-len", type=int, default=43)
+    ap.add_argument("--batches", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--write-corpus", default=None)
+    args = ap.parse_args()
+    if args.write_corpus:
+        return write_corpus(args.write_corpus)
+    from plenum_amd import EdVerifyEngine
+    from plenum_amd.client_authn import GpuAuthNr
+    eng = EdVerifyEngine(0)
+    t0 = time.perf_counter()
+    texts, dicts, idrs, vks = build(eng, args.n, args.signers, args.alias_len)
+    print("built %d requests, %.0f B mean text, in %.1f s" % (
+        args.n, sum(len(t) for t in texts[:1000]) / min(args.n, 1000), time.perf_counter() - t0), flush=True)
+    a = GpuAuthNr(engine=eng)
+    for idr, vk in zip(idrs, vks):
+        a.addIdr(idr, vk)
+    a.keys_settle()
+    paths = {
+        "wire": lambda: a.authenticate_wire_batch(texts),
+        "dicts": lambda: a.authenticate_batch(dicts),
+        "loads_dicts": lambda: a.authenticate_batch([json.loads(t) for t in texts]),
+    }
+    for _ in range(2):  # warm-up: buffers grown, kernels loaded
+        for f in paths.values():
+            f()
+    host0 = a.stats["wire_host_items"]
+    times = {k: [] for k in paths}
+    breakdown = []
+    for _ in range(args.batches):
+        res = {}
+        for name, f in paths.items():
+            t0 = time.perf_counter()
+            res[name] = f()
+            times[name].append(time.perf_counter() - t0)
+            if name == "wire":
+                breakdown.append(dict(a._g.last_wire_breakdown))
+        assert res["wire"] == res["dicts"] == res["loads_dicts"], "verdicts differ between the paths"
+        assert all(r.__class__ is str for r in res["wire"]), "a request of the all-valid batch failed"
+        del res
+    assert a.stats["wire_host_items"] == host0, "the wire scan left items to the host"
+    out = {"n": args.n, "signers": args.signers, "batches": args.batches,
+           "mean_text_bytes": sum(map(len, texts)) / args.n}
+    for name, ts in times.items():
+        p50 = statistics.median(ts)
+        out[name] = {"p50_ms": round(p50 * 1e3, 3), "min_ms": round(min(ts) * 1e3, 3),
+                     "max_ms": round(max(ts) * 1e3, 3),
+                     "M_requests_per_s": round(args.n / p50 / 1e6, 3)}
+    out["wire_breakdown_p50_ms"] = {k: round(statistics.median(b[k] for b in breakdown), 3)
+                                    for k in ("gather", "scan", "keys", "verify", "results")}
+    out["wire_breakdown_note"] = ("gather = texts into pinned memory; scan = PCIe + edv_wire_scan_kernel + status "
+                                  "read-back; "
+                                  "keys = distinct identifiers, getVerkey, key ids; verify = edv_wire_verify; "
+                                  "results = the result list")
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
