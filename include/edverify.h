@@ -377,6 +377,18 @@ int edv_wire_scan(edv_ctx *ctx, const uint8_t *text, const uint64_t *text_off, u
  * bit 0 (no key / the host decides).  Same verdicts as edv_verify_batch(_keyed) on the same bytes.
  * pk32 may be NULL when no item uses it; n is the wire batch's item count. */
 int edv_wire_verify(edv_ctx *ctx, const uint32_t *key_id, const uint8_t *pk32, uint64_t n, uint8_t *accept_bits);
+/* The wire batch's distinct identifiers, found on the GPU from what the scan left in HBM
+ * (csrc/wire_idents.h): uidx[n] = per item the index of its identifier among the distinct ones in
+ * first-occurrence order (*n_uniq for an item with status != 0), uniq_item[0 .. *n_uniq) = the item
+ * of each identifier's first occurrence (room for n entries).  uidx also stays in HBM for
+ * edv_wire_verify_idents until the next edv_wire_scan.  EDV_EINVAL without a wire batch. */
+int edv_wire_idents(edv_ctx *ctx, uint32_t *uidx, uint32_t *uniq_item, uint64_t *n_uniq);
+/* edv_wire_verify for the steady state, with one key id per distinct identifier: the verdicts of
+ * edv_wire_verify(key_id[i] = kid_u[uidx[i]]), bit for bit; only the n_uniq ids cross PCIe.
+ * Needs every item scanned (status 0) and every kid_u[j] a key id (< EDV_WIRE_SKIP); EDV_EINVAL
+ * otherwise, with no uidx of this batch (edv_wire_idents not called, or the batch rescanned
+ * since), or with n_uniq not the batch's count -- the caller then uses edv_wire_verify. */
+int edv_wire_verify_idents(edv_ctx *ctx, const uint32_t *kid_u, uint64_t n_uniq, uint8_t *accept_bits);
 /* DIAGNOSTIC: read the wire batch back -- sig64[n*64], msgs (item i at text_off[i]-text_off[0]),
  * msg_len[n] -- so tests compare bytes, not only verdicts.  Items with status != 0 read as zero
  * length; their sig64 and msgs bytes are unspecified. */

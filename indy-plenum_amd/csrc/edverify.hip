@@ -18,6 +18,10 @@
 //                           ballot into the accept bitmask.
 //   edv_wire_scan_kernel   request texts from the wire -> decoded signatures,
 //                          identifier spans and signing bytes in HBM (wire_scan.h)
+//   edv_wire_ident_insert_kernel / _flag_kernel / _number_kernel   the wire batch's
+//                          distinct identifiers in first-occurrence order and each
+//                          item's index into them (wire_idents.h);
+//   edv_wire_ident_keys_kernel   per-item key ids from per-identifier ones
 //   edv_sign_kernel / edv_keypair_kernel   deterministic Ed25519 signer
 //   edv_tally_*          distinct-voter ballots -> counts -> quorum flags.
 #include <hip/hip_runtime.h>
@@ -46,6 +50,7 @@
 #include "fe_lanes.h"
 #include "sha256.h"
 #include "verify_core.h"
+#include "wire_idents.h"
 #include "wire_scan.h"
 
 using namespace edv;
@@ -727,6 +732,76 @@ __global__ __launch_bounds__(kWireThreads) void edv_wire_scan_kernel(
     __syncthreads();  // every lane has read s_next / s_lo / s_hi and s_out before the next tile resets them
     t0 = next & ~15ull;
   }
+}
+
+// ---- the wire batch's distinct identifiers (edverify.h edv_wire_idents; the lane code is wire_idents.h)
+// One lane per item over what the scan left in HBM.  insert: the status-0 items into the table
+// (owner / first, kIdentEmpty beforehand), slot[i] = the item's slot; an item whose identifier
+// span is not inside its text gets no slot and raises *bad (never read).  flag (after the kernel
+// boundary: first[] is final): flag[i] = the item is its identifier's first occurrence, n + 1
+// entries, the last one 0, so that their exclusive sum `rank` ends in the number of identifiers.
+// number: uidx[i] = the rank of the item's identifier (rank[n] for an item without a slot) and
+// the first occurrences' indices in rank order.  keys: w_keys[i] = kid_u[uidx[i]].
+struct WireText {  // byte b of the caller's buffer
+  const uint8_t* p;
+  uint64_t base;
+  __device__ __forceinline__ uint32_t operator[](uint64_t b) const { return p[b - base]; }
+};
+struct WireIdentTable {
+  uint32_t* owner;
+  uint32_t* first;
+  __device__ __forceinline__ uint32_t owner_load(uint32_t s) const {
+    return __hip_atomic_load(owner + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ uint32_t owner_cas(uint32_t s, uint32_t i) const { return atomicCAS(owner + s, kIdentEmpty, i); }
+  __device__ __forceinline__ uint32_t first_load(uint32_t s) const {
+    return __hip_atomic_load(first + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ void first_min(uint32_t s, uint32_t i) const { atomicMin(first + s, i); }
+};
+
+__global__ __launch_bounds__(kBlock) void edv_wire_ident_insert_kernel(
+    const uint8_t* __restrict__ text, const uint64_t* __restrict__ off, uint64_t base, uint64_t n,
+    const uint8_t* __restrict__ status, const uint32_t* __restrict__ span, uint32_t* owner, uint32_t* first,
+    uint32_t cap, uint32_t* __restrict__ slot, uint32_t* __restrict__ bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t s = kIdentEmpty;
+  if (status[i] == (uint8_t)kWireOk) {
+    if (wi_span_ok(off, span, i))
+      s = wi_insert(WireText{text, base}, off, span, WireIdentTable{owner, first}, cap, (uint32_t)i);
+    if (s == kIdentEmpty) *bad = 1;
+  }
+  slot[i] = s;
+}
+
+__global__ __launch_bounds__(kBlock) void edv_wire_ident_flag_kernel(uint64_t n, const uint32_t* __restrict__ slot,
+                                                                    const uint32_t* __restrict__ first,
+                                                                    uint32_t* __restrict__ flag) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  flag[i] = i < n ? wi_flag(slot, first, i) : 0u;
+}
+
+__global__ __launch_bounds__(kBlock) void edv_wire_ident_number_kernel(uint64_t n, const uint32_t* __restrict__ slot,
+                                                                      const uint32_t* __restrict__ first,
+                                                                      const uint32_t* __restrict__ flag,
+                                                                      const uint32_t* __restrict__ rank,
+                                                                      uint32_t* __restrict__ uidx,
+                                                                      uint32_t* __restrict__ uniq_item) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uidx[i] = wi_index(slot, first, rank, n, i);
+  if (flag[i]) uniq_item[rank[i]] = (uint32_t)i;  // (rank[i] < rank[n] <= n)
+}
+
+__global__ __launch_bounds__(kBlock) void edv_wire_ident_keys_kernel(uint64_t n, const uint32_t* __restrict__ uidx,
+                                                                    const uint32_t* __restrict__ kid_u, uint32_t nu,
+                                                                    uint32_t* __restrict__ keys) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t u = uidx[i];
+  keys[i] = u < nu ? kid_u[u] : EDV_WIRE_SKIP;  // (every item has an identifier: checked on the host)
 }
 
 // ---- key order of the comb (edv_options.key_sort) ------------------------------
@@ -2045,8 +2120,14 @@ struct edv_ctx {
   // that is not pinned and for the results; the status bytes kept on the host for the verify
   Buf w_text, w_msg, w_sig, w_spans, w_status, w_idr, w_off, w_keys, w_words;
   Buf wh_text, wh_off, wh_out, wh_keys, wh_bits;
-  uint64_t wire_n = 0, wire_bytes = 0;
+  uint64_t wire_n = 0, wire_bytes = 0, wire_base = 0;
   bool wire_ok = false;
+  // edv_wire_idents: the table (owner [cap] then first [cap]), per item its slot, flag, rank
+  // ([n + 1] each) and index (w_uidx, kept for edv_wire_verify_idents until the next scan), the
+  // first occurrences, the scan's scratch, a flag word, the per-identifier key ids; pinned staging
+  Buf w_itab, w_islot, w_iflag, w_irank, w_uidx, w_uitem, w_itmp, w_ibad, w_ikid, wh_idents, wh_ikid;
+  bool wire_uidx_ok = false, wire_all_live = false;
+  uint64_t wire_nu = 0;
   std::vector<uint8_t> wire_status;
   std::vector<hipEvent_t> wire_ev;  // one per upload chunk of a scan (+ 1), made on first use
   Buf& d_stage() { return d_stage_set[cur_set]; }
@@ -3566,6 +3647,7 @@ int edv_wire_scan(edv_ctx* ctx, const uint8_t* text, const uint64_t* text_off, u
   int r = set_device(ctx);
   if (r) return r;
   ctx->wire_ok = false;
+  ctx->wire_uidx_ok = false;
   if (!text_off || (n && (!status || !idr_span))) return set_err(EDV_EINVAL, "null pointer");
   if (n >= EDV_WIRE_SKIP) return set_err(EDV_EINVAL, "too many items");
   uint64_t bad = 0;
@@ -3575,6 +3657,7 @@ int edv_wire_scan(edv_ctx* ctx, const uint8_t* text, const uint64_t* text_off, u
   if (total && !text) return set_err(EDV_EINVAL, "null text");
   ctx->wire_n = n;
   ctx->wire_bytes = total;
+  ctx->wire_base = base;
   ctx->wire_status.assign((size_t)n, (uint8_t)EDV_WIRE_HOST);
   if (n == 0) {
     ctx->wire_ok = true;
@@ -3726,6 +3809,124 @@ int edv_wire_verify(edv_ctx* ctx, const uint32_t* key_id, const uint8_t* pk32, u
         idx.push_back((uint32_t)i);
     if ((r = wire_verify_group(ctx, keyed != 0, idx, key_id, pk32, accept_bits))) return r;
   }
+  return 0;
+}
+
+// first occurrences read back with the indices, before their count is known (more: a second copy)
+constexpr uint64_t kWireUniqEager = 4096;
+
+int edv_wire_idents(edv_ctx* ctx, uint32_t* uidx, uint32_t* uniq_item, uint64_t* n_uniq) {
+  int r = set_device(ctx);
+  if (r) return r;
+  if (!ctx->wire_ok) return set_err(EDV_EINVAL, "no wire batch (edv_wire_scan first)");
+  if (!n_uniq) return set_err(EDV_EINVAL, "null pointer");
+  *n_uniq = 0;
+  ctx->wire_uidx_ok = false;
+  const uint64_t n = ctx->wire_n;
+  if (n == 0) {
+    ctx->wire_nu = 0;
+    ctx->wire_all_live = true;
+    ctx->wire_uidx_ok = true;
+    return 0;
+  }
+  if (!uidx || !uniq_item) return set_err(EDV_EINVAL, "null pointer");
+  if (n > (1ull << 30)) return set_err(EDV_EINVAL, "too many items for the identifier table");
+  uint64_t cap = 64;
+  while (cap < 2 * n) cap <<= 1;  // never full: every probe ends at the identifier's slot or a free one
+  hipStream_t st = ctx->stream;
+  size_t tmp = 0;
+  HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)(n + 1),
+                                  rocprim::plus<uint32_t>(), st));
+  const uint64_t eager = n < kWireUniqEager ? n : kWireUniqEager;
+  if ((r = ensure(ctx->w_itab, 8 * cap)) || (r = ensure(ctx->w_islot, 4 * n)) || (r = ensure(ctx->w_iflag, 4 * (n + 1))) ||
+      (r = ensure(ctx->w_irank, 4 * (n + 1))) || (r = ensure(ctx->w_uidx, 4 * n)) || (r = ensure(ctx->w_uitem, 4 * n)) ||
+      (r = ensure(ctx->w_itmp, tmp)) || (r = ensure(ctx->w_ibad, 16)) || (r = ensure_pinned(ctx->wh_idents, 16 + 8 * n)))
+    return r;
+  uint32_t* owner = (uint32_t*)ctx->w_itab.p;
+  uint32_t* first = owner + cap;
+  uint32_t *slot = (uint32_t*)ctx->w_islot.p, *flag = (uint32_t*)ctx->w_iflag.p, *rank = (uint32_t*)ctx->w_irank.p;
+  uint32_t *d_uidx = (uint32_t*)ctx->w_uidx.p, *d_uitem = (uint32_t*)ctx->w_uitem.p, *d_bad = (uint32_t*)ctx->w_ibad.p;
+  HIP_TRY(hipMemsetAsync(owner, 0xff, 8 * cap, st));
+  HIP_TRY(hipMemsetAsync(d_bad, 0, 4, st));
+  const dim3 grid((uint32_t)div_up(n + 1, kBlock)), block(kBlock);
+  hipLaunchKernelGGL(edv_wire_ident_insert_kernel, grid, block, 0, st, (const uint8_t*)ctx->w_text.p + kWirePad,
+                     (const uint64_t*)ctx->w_off.p, ctx->wire_base, n, (const uint8_t*)ctx->w_status.p,
+                     (const uint32_t*)ctx->w_idr.p, owner, first, (uint32_t)cap, slot, d_bad);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(edv_wire_ident_flag_kernel, grid, block, 0, st, n, (const uint32_t*)slot, (const uint32_t*)first,
+                     flag);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(rocprim::exclusive_scan(ctx->w_itmp.p, tmp, flag, rank, 0u, (size_t)(n + 1), rocprim::plus<uint32_t>(), st));
+  hipLaunchKernelGGL(edv_wire_ident_number_kernel, grid, block, 0, st, n, (const uint32_t*)slot, (const uint32_t*)first,
+                     (const uint32_t*)flag, (const uint32_t*)rank, d_uidx, d_uitem);
+  HIP_TRY(hipGetLastError());
+  // pinned staging: [0] the number of identifiers, [1] the bad-span flag, [4 ..) the indices, then
+  // the first occurrences; a caller's pinned array takes its copy directly
+  uint32_t* h = (uint32_t*)ctx->wh_idents.p;
+  uint32_t* h_uidx = pinned_range(uidx, 4 * n) ? uidx : h + 4;
+  uint32_t* h_uitem = h + 4 + n;
+  HIP_TRY(hipMemcpyAsync(h, rank + n, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h + 1, d_bad, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_uidx, d_uidx, 4 * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_uitem, d_uitem, 4 * eager, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint64_t nu = h[0];
+  if (h[1] || nu > n) return set_err(EDV_EINVAL, "an identifier span outside its item");
+  if (nu > eager) {
+    HIP_TRY(hipMemcpyAsync(h_uitem + eager, d_uitem + eager, 4 * (nu - eager), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  if (h_uidx != uidx) memcpy(uidx, h_uidx, 4 * n);
+  memcpy(uniq_item, h_uitem, 4 * nu);
+  uint64_t host_items = 0;
+  const uint8_t* status = ctx->wire_status.data();
+  for (uint64_t i = 0; i < n; ++i) host_items += (uint64_t)(status[i] != EDV_WIRE_OK);
+  ctx->wire_all_live = host_items == 0;
+  ctx->wire_nu = nu;
+  ctx->wire_uidx_ok = true;
+  *n_uniq = nu;
+  return 0;
+}
+
+int edv_wire_verify_idents(edv_ctx* ctx, const uint32_t* kid_u, uint64_t n_uniq, uint8_t* accept_bits) {
+  int r = set_device(ctx);
+  if (r) return r;
+  if (!ctx->wire_ok) return set_err(EDV_EINVAL, "no wire batch (edv_wire_scan first)");
+  if (!ctx->wire_uidx_ok) return set_err(EDV_EINVAL, "no identifier indices for this wire batch (edv_wire_idents first)");
+  if (n_uniq != ctx->wire_nu)
+    return set_err(EDV_EINVAL, "the wire batch holds %llu identifiers", (unsigned long long)ctx->wire_nu);
+  const uint64_t n = ctx->wire_n;
+  if (n == 0) return 0;
+  if (!ctx->wire_all_live) return set_err(EDV_EINVAL, "an item the host decides (edv_wire_verify takes those)");
+  if (!kid_u || !accept_bits) return set_err(EDV_EINVAL, "null pointer");
+  uint64_t unkeyed = 0;
+  for (uint64_t j = 0; j < n_uniq; ++j) unkeyed += (uint64_t)(kid_u[j] >= EDV_WIRE_SKIP);
+  if (unkeyed) return set_err(EDV_EINVAL, "an identifier without a key id (edv_wire_verify takes those)");
+  if (ctx->key_count == 0) return set_err(EDV_EINVAL, "no registered keys");
+  const uint64_t nwords = div_up(n, 64);
+  if ((r = ensure(ctx->w_keys, 4 * n)) || (r = ensure(ctx->w_words, 8 * nwords)) || (r = ensure(ctx->w_ikid, 4 * n_uniq)) ||
+      (r = ensure_pinned(ctx->wh_bits, 8 * nwords)))
+    return r;
+  const void* src = kid_u;
+  if (!pinned_range(kid_u, 4 * n_uniq)) {
+    if ((r = ensure_pinned(ctx->wh_ikid, 4 * n_uniq))) return r;
+    memcpy(ctx->wh_ikid.p, kid_u, 4 * n_uniq);
+    src = ctx->wh_ikid.p;
+  }
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemcpyAsync(ctx->w_ikid.p, src, 4 * n_uniq, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(edv_wire_ident_keys_kernel, dim3((uint32_t)div_up(n, kBlock)), dim3(kBlock), 0, st, n,
+                     (const uint32_t*)ctx->w_uidx.p, (const uint32_t*)ctx->w_ikid.p, (uint32_t)n_uniq,
+                     (uint32_t*)ctx->w_keys.p);
+  HIP_TRY(hipGetLastError());
+  const uint64_t* ms = (const uint64_t*)ctx->w_spans.p;
+  set_bucketing(ctx, false);
+  r = launch_pipeline(ctx, true, ctx->w_sig.p, ctx->w_keys.p, ctx->w_msg.p, ms, ms + n, n, ctx->w_words.p, st);
+  if (r) return r;
+  HIP_TRY(hipMemcpyAsync(ctx->wh_bits.p, ctx->w_words.p, 8 * nwords, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  memcpy(accept_bits, ctx->wh_bits.p, (size_t)((n + 7) / 8));
+  if (n & 7) accept_bits[n / 8] &= (uint8_t)((1u << (n & 7)) - 1);
   return 0;
 }
 
@@ -3933,7 +4134,9 @@ void edv_destroy(edv_ctx* ctx) {
                           &ctx->sub_h, &ctx->sub_d_in, &ctx->sub_d_sig, &ctx->sub_d_spans, &ctx->sub_d_words,
                           &ctx->sub_h_bits, &ctx->w_text, &ctx->w_msg, &ctx->w_sig, &ctx->w_spans, &ctx->w_status,
                           &ctx->w_idr, &ctx->w_off, &ctx->w_keys, &ctx->w_words, &ctx->wh_text, &ctx->wh_off,
-                          &ctx->wh_out, &ctx->wh_keys, &ctx->wh_bits})
+                          &ctx->wh_out, &ctx->wh_keys, &ctx->wh_bits, &ctx->w_itab, &ctx->w_islot, &ctx->w_iflag,
+                          &ctx->w_irank, &ctx->w_uidx, &ctx->w_uitem, &ctx->w_itmp, &ctx->w_ibad, &ctx->w_ikid,
+                          &ctx->wh_idents, &ctx->wh_ikid})
     free_buf(*b);
   for (int k = 0; k < edv_ctx::kSets; ++k) {
     for (edv_ctx::Buf* b : {&ctx->d_stage_set[k], &ctx->d_spans[k], &ctx->s_sig[k], &ctx->s_key[k], &ctx->s_bits[k],

@@ -530,3 +530,81 @@ void hc_wire_scan(const uint8_t* text, const uint64_t* off, uint64_t n, uint8_t*
   }
 }
 }  // extern "C"
+
+// ---- the wire batch's distinct identifiers (wire_idents.h, the code of edv_wire_ident_*_kernel's
+// lanes) on the CPU, every read and write asserted in bounds, for tests/test_wire_idents.py.
+#include "wire_idents.h"
+namespace {
+template <class V>
+struct CheckedArr {
+  V* p;
+  uint64_t n;
+  V& operator[](uint64_t i) const {
+    EDV_ASSERT(i < n);
+    return p[i];
+  }
+};
+struct CheckedBytes {  // the texts, by their position in the caller's buffer
+  const uint8_t* p;
+  uint64_t lo, hi;
+  uint8_t operator[](uint64_t i) const {
+    EDV_ASSERT(i >= lo && i < hi);
+    return p[i];
+  }
+};
+struct SerialTable {  // the device's atomics, one item at a time
+  CheckedArr<uint32_t> owner, first;
+  uint32_t owner_load(uint32_t s) const { return owner[s]; }
+  uint32_t owner_cas(uint32_t s, uint32_t i) const {
+    const uint32_t was = owner[s];
+    if (was == kIdentEmpty) owner[s] = i;
+    return was;
+  }
+  uint32_t first_load(uint32_t s) const { return first[s]; }
+  void first_min(uint32_t s, uint32_t i) const {
+    if (i < first[s]) first[s] = i;
+  }
+};
+}  // namespace
+extern "C" {
+// The distinct identifiers of the status-0 items of n texts (item i = text[off[i] .. off[i + 1]),
+// identifier span[2i], span[2i + 1] inside it), the items inserted in the order order[0 .. n) (a
+// permutation) into a table of cap slots (a power of two, at least the number of identifiers):
+// uidx[n] = the item's index among the identifiers in first-occurrence order (nu elsewhere),
+// uniq_item[0 .. nu) = each identifier's first item.  Returns nu; -1 a span outside its item (no
+// byte outside the texts is read), -2 a table that is too small or not a power of two.
+int64_t hc_wire_idents(const uint8_t* text, const uint64_t* off_p, uint64_t n, const uint8_t* status_p,
+                       const uint32_t* span_p, uint64_t cap, const uint32_t* order_p, uint32_t* uidx_p,
+                       uint32_t* uniq_item_p) {
+  if (cap == 0 || (cap & (cap - 1)) || cap > 0x80000000ull) return -2;
+  const CheckedArr<const uint64_t> off{off_p, n + 1};
+  const CheckedArr<const uint8_t> status{status_p, n};
+  const CheckedArr<const uint32_t> span{span_p, 2 * n}, order{order_p, n};
+  const CheckedArr<uint32_t> uidx{uidx_p, n}, uniq_item{uniq_item_p, n};
+  const CheckedBytes t{text, off[0], off[n]};
+  std::vector<uint32_t> owner_v((size_t)cap, kIdentEmpty), first_v((size_t)cap, kIdentEmpty);
+  std::vector<uint32_t> slot_v((size_t)n + 1, kIdentEmpty), flag_v((size_t)n + 1, 0), rank_v((size_t)n + 1, 0);
+  const SerialTable tab{{owner_v.data(), cap}, {first_v.data(), cap}};
+  const CheckedArr<uint32_t> slot{slot_v.data(), n}, flag{flag_v.data(), n + 1}, rank{rank_v.data(), n + 1};
+  bool bad = false, full = false;
+  for (uint64_t k = 0; k < n; ++k) {
+    const uint32_t i = order[k];
+    if (status[i] != 0) continue;
+    if (!wi_span_ok(off, span, i)) {
+      bad = true;
+      continue;
+    }
+    slot[i] = wi_insert(t, off, span, tab, (uint32_t)cap, i);
+    full |= slot[i] == kIdentEmpty;
+  }
+  if (bad) return -1;
+  if (full) return -2;
+  for (uint64_t i = 0; i < n; ++i) flag[i] = wi_flag(slot, tab.first, i);
+  for (uint64_t i = 0; i < n; ++i) rank[i + 1] = rank[i] + flag[i];
+  for (uint64_t i = 0; i < n; ++i) {
+    uidx[i] = wi_index(slot, tab.first, rank, n, i);
+    if (flag[i]) uniq_item[rank[i]] = (uint32_t)i;
+  }
+  return (int64_t)rank[n];
+}
+}  // extern "C"

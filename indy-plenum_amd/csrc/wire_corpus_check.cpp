@@ -2,7 +2,10 @@
 // edv_wire_scan_kernel) over a corpus file on the host CPU, as a stand-alone program meant to
 // be built with -fsanitize=address,undefined (Makefile target wire-corpus-check).  Every text is
 // copied into a heap block of exactly its length and scanned into another of the same length, so
-// a read or write one byte outside either is reported.
+// a read or write one byte outside either is reported.  Then the corpus as one wire batch -- the
+// texts back to back in a heap block of exactly their total length -- through the identifier pass
+// (wire_idents.h, the lane code of edv_wire_ident_*_kernel) with a table of 2 n slots and again
+// with one just large enough, whose chains wrap.
 //
 // Corpus file: per text a little-endian uint32 length, then the bytes
 // (tools/wire_probe.py --write-corpus FILE writes the test corpus in this form).
@@ -12,7 +15,51 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <vector>
+
+#include "wire_idents.h"
 #include "wire_scan.h"
+
+namespace {
+struct SerialTable {  // the device's atomics, one item at a time
+  uint32_t* owner;
+  uint32_t* first;
+  uint32_t owner_load(uint32_t s) const { return owner[s]; }
+  uint32_t owner_cas(uint32_t s, uint32_t i) const {
+    const uint32_t was = owner[s];
+    if (was == edv::kIdentEmpty) owner[s] = i;
+    return was;
+  }
+  uint32_t first_load(uint32_t s) const { return first[s]; }
+  void first_min(uint32_t s, uint32_t i) const {
+    if (i < first[s]) first[s] = i;
+  }
+};
+
+// The number of distinct identifiers of the status-0 items, or -1 when the table is too small.
+long idents(const uint8_t* text, const std::vector<uint64_t>& off, const std::vector<uint8_t>& status,
+            const std::vector<uint32_t>& span, uint64_t cap) {
+  const uint64_t n = status.size();
+  uint32_t* owner = (uint32_t*)malloc(cap * 4);  // (heap blocks of the exact size, as the texts)
+  uint32_t* first = (uint32_t*)malloc(cap * 4);
+  uint32_t* slot = (uint32_t*)malloc((n ? n : 1) * 4);
+  memset(owner, 0xff, cap * 4);
+  memset(first, 0xff, cap * 4);
+  long nu = 0;
+  for (uint64_t k = 0; k < n && nu >= 0; ++k) {
+    const uint64_t i = n - 1 - k;  // (any order gives the same answer: the last item first)
+    slot[i] = edv::kIdentEmpty;
+    if (status[i] != 0 || !edv::wi_span_ok(off.data(), span.data(), i)) continue;
+    slot[i] = edv::wi_insert(text, off.data(), span.data(), SerialTable{owner, first}, (uint32_t)cap, (uint32_t)i);
+    if (slot[i] == edv::kIdentEmpty) nu = -1;
+  }
+  for (uint64_t i = 0; i < n && nu >= 0; ++i) nu += edv::wi_flag(slot, first, i);
+  free(owner);
+  free(first);
+  free(slot);
+  return nu;
+}
+}  // namespace
 
 int main(int argc, char** argv) {
   if (argc != 2) {
@@ -25,6 +72,9 @@ int main(int argc, char** argv) {
     return 2;
   }
   uint64_t texts = 0, scanned = 0, host = 0, out_bytes = 0;
+  std::vector<uint8_t> all, status;
+  std::vector<uint64_t> off(1, 0);
+  std::vector<uint32_t> span;
   for (;;) {
     uint8_t hdr[4];
     const size_t got = fread(hdr, 1, 4, f);
@@ -58,11 +108,31 @@ int main(int argc, char** argv) {
     } else {
       ++host;
     }
+    all.insert(all.end(), text, text + len);
+    off.push_back(all.size());
+    status.push_back((uint8_t)st);
+    span.push_back(st == edv::kWireOk ? it.idr_start : 0);
+    span.push_back(st == edv::kWireOk ? it.idr_len : 0);
     free(text);
     free(out);
   }
   fclose(f);
   printf("texts %llu scanned %llu host %llu serialized bytes %llu\n", (unsigned long long)texts,
          (unsigned long long)scanned, (unsigned long long)host, (unsigned long long)out_bytes);
+  uint8_t* batch = (uint8_t*)malloc(all.size() ? all.size() : 1);
+  memcpy(batch, all.data(), all.size());
+  uint64_t cap = 64;
+  while (cap < 2 * texts) cap <<= 1;
+  const long nu = idents(batch, off, status, span, cap);
+  uint64_t tight = 1;
+  while ((long)tight < nu) tight <<= 1;
+  const long nu_tight = idents(batch, off, status, span, tight);
+  free(batch);
+  printf("identifiers %ld (table of %llu slots) %ld (of %llu)\n", nu, (unsigned long long)cap, nu_tight,
+         (unsigned long long)tight);
+  if (nu < 0 || nu_tight != nu) {
+    fprintf(stderr, "the identifier pass disagrees with itself\n");
+    return 1;
+  }
   return 0;
 }

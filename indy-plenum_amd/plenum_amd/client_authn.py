@@ -341,6 +341,9 @@ class _GpuState:
                       "keys_registered": 0, "prefetched": 0, "wire_items": 0, "wire_host_items": 0}
         self.wire_bytes_per_item = 400.0  # sizes the next wire batch's pinned text buffer
         self.last_wire_breakdown = None  # the last wire batch's phases (ms)
+        # the wire batch's distinct identifiers on the GPU (engine.wire_idents, on an engine with
+        # supports_wire_idents); EDV_WIRE_IDENTS=0: the host pass (_hostpack.wire_idents), for A/B runs
+        self.wire_idents_gpu = os.environ.get("EDV_WIRE_IDENTS", "1") != "0"
 
 
 class GpuAuthMixin:
@@ -1660,8 +1663,17 @@ class GpuAuthMixin:
             t1 = _perf_counter()
             status, span = eng.wire_scan(np.frombuffer(buf, np.uint8), off)
             t2 = _perf_counter()
-            uidx_b, uniq = _wire_idents(buf, off_b, status, span, g.scan_threads)
-            uidx = np.frombuffer(uidx_b, np.uint32)
+            on_gpu = g.wire_idents_gpu and getattr(eng, "supports_wire_idents", False)
+            if on_gpu:  # the host sees the distinct identifiers only: one slice of the text each
+                pinned = self._pinned(eng, "wire_uidx", 4 * n)
+                uidx, uniq_item = eng.wire_idents() if pinned is None else eng.wire_idents(pinned)
+                uidx_b = uidx.data
+                text = memoryview(buf)
+                at = off[uniq_item] + span[uniq_item, 0]
+                uniq = [str(text[a:b], "ascii") for a, b in zip(at.tolist(), (at + span[uniq_item, 1]).tolist())]
+            else:
+                uidx_b, uniq = _wire_idents(buf, off_b, status, span, g.scan_threads)
+                uidx = np.frombuffer(uidx_b, np.uint32)
             nu = len(uniq)
             ukeys = self._keys_for(uniq)  # authenticate():93-99, once per identifier
             # per distinct identifier (one more for the items the scan left to the host): 0 = a
@@ -1694,19 +1706,23 @@ class GpuAuthMixin:
                     kid_u[j] = eng.WIRE_NO_ID
                 else:
                     kid_u[j] = i
-            # (one native pass: numpy's fancy indexing widens the index array to intp first)
-            key_id = np.frombuffer(_gather_u32(kid_u.tobytes(), uidx_b), np.uint32) if _gather_u32 is not None \
-                else kid_u[uidx]
+            steady = not general_u and not status.any() and not cls_u[:nu].any()
+            if on_gpu and steady:
+                key_id = None  # (the GPU gathers the per-item ids from kid_u)
+            else:
+                # (one native pass: numpy's fancy indexing widens the index array to intp first)
+                key_id = np.frombuffer(_gather_u32(kid_u.tobytes(), uidx_b), np.uint32) if _gather_u32 is not None \
+                    else kid_u[uidx]
             pk32 = None
             if general_u:
                 pk_u = np.zeros((nu + 1, 32), np.uint8)
                 pk_u[general_u] = np.frombuffer(b"".join(ukeys[j] for j in general_u), np.uint8).reshape(-1, 32)
                 pk32 = pk_u[uidx]
-            if not general_u and not status.any() and not cls_u[:nu].any():
+            if steady:
                 # every text scanned, every identifier's key registered (the node's steady state):
                 # no per-item class array
                 t3 = _perf_counter()
-                ok = eng.wire_verify(key_id, None)
+                ok = eng.wire_verify_idents(kid_u[:nu]) if on_gpu else eng.wire_verify(key_id, None)
                 t4 = _perf_counter()
                 g.stats["batches"] += 1
                 g.stats["batch_items"] += n

@@ -353,6 +353,37 @@ class EdVerifyEngine:
                                         _ptr(bits) if n else None))
         return unpack_bits(bits, n)
 
+    supports_wire_idents = True
+
+    def wire_idents(self, out=None):
+        """The wire batch's distinct identifiers, found on the GPU
+        (edv_wire_idents): (uidx uint32[n] -- per item the index of its
+        identifier among the distinct ones in first-occurrence order, nu for an
+        item with status != 0 --, uniq_item uint32[nu] -- the item of each
+        identifier's first occurrence).  uidx also stays in HBM for
+        wire_verify_idents until the next wire_scan.  out: a writable buffer
+        of 4 n bytes or more that uidx becomes a view of (host_alloc memory
+        is DMA'd into in place)."""
+        n = getattr(self, "_wire_shape", (0, 0))[0]
+        uidx = np.empty(n, np.uint32) if out is None else np.frombuffer(out, np.uint32, count=n)
+        uniq_item = np.empty(n, np.uint32)
+        nu = ctypes.c_uint64(0)
+        check(self._lib.edv_wire_idents(self._ctx, _ptr(uidx) if n else None, _ptr(uniq_item) if n else None,
+                                        ctypes.byref(nu)))
+        return uidx, uniq_item[:nu.value]
+
+    def wire_verify_idents(self, kid_u):
+        """wire_verify(kid_u[uidx]) for the steady state, with uidx as
+        wire_idents left it in HBM (edv_wire_verify_idents): every item scanned,
+        kid_u uint32[nu] all registered key ids.  Any other batch is an error
+        (code -1): wire_verify takes it."""
+        kid_u = np.ascontiguousarray(kid_u, dtype=np.uint32)
+        n = getattr(self, "_wire_shape", (0, 0))[0]
+        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
+        check(self._lib.edv_wire_verify_idents(self._ctx, _ptr(kid_u) if kid_u.size else None, kid_u.shape[0],
+                                               _ptr(bits) if n else None))
+        return unpack_bits(bits, n)
+
     def wire_readback(self):
         """DIAGNOSTIC (edv_wire_readback): the wire batch's (sig64 uint8[n, 64],
         msgs uint8[text bytes] -- item i's serialization at text_off[i] -

@@ -8,7 +8,11 @@ the wire path must leave no item to the host.  Prints one JSON line: the three r
 p50 ms per batch, and the wire path's breakdown (gather, PCIe + scan kernel, key
 resolution, verify, result list).
 
-usage: python tools/wire_probe.py [--n 1000000] [--signers 1000] [--batches 10] [--out FILE]
+--idents-ab: path (a) alone, two ways alternating in one process: the batch's distinct identifiers
+found on the GPU (EDV_WIRE_IDENTS=1: edv_wire_idents, edv_wire_verify_idents) and on the host
+(EDV_WIRE_IDENTS=0: _hostpack.wire_idents); p50 and min-max of the `keys` phase and of the batch.
+
+usage: python tools/wire_probe.py [--n 1000000] [--signers 1000] [--batches 10] [--out FILE] [--idents-ab]
        python tools/wire_probe.py --write-corpus FILE   (no GPU: the test corpus, length-prefixed,
                                                          for indy-plenum_amd/build/wire_corpus_check)
 """
@@ -58,6 +62,47 @@ def build(eng, n, signers, alias_len):
     return texts, dicts, idrs, ["~" + b58encode(bytes(pk[16:])) for pk in pks]
 
 
+def idents_ab(eng, args, texts, idrs, vks):
+    """Path (a) with the identifier pass on the GPU and on the host, alternating."""
+    from plenum_amd.client_authn import GpuAuthNr
+    auth = {}
+    for name, env in (("gpu_idents", "1"), ("host_idents", "0")):
+        os.environ["EDV_WIRE_IDENTS"] = env  # read when the authenticator is made
+        a = auth[name] = GpuAuthNr(engine=eng)
+        for idr, vk in zip(idrs, vks):
+            a.addIdr(idr, vk)
+        a.keys_settle()
+    os.environ.pop("EDV_WIRE_IDENTS")
+    assert auth["gpu_idents"]._g.wire_idents_gpu and not auth["host_idents"]._g.wire_idents_gpu
+    for _ in range(2):
+        for a in auth.values():
+            a.authenticate_wire_batch(texts)
+    phases = ("gather", "scan", "keys", "verify", "results")
+    times = {k: [] for k in auth}
+    breakdown = {k: [] for k in auth}
+    for _ in range(args.batches):
+        res = {}
+        for name, a in auth.items():
+            t0 = time.perf_counter()
+            res[name] = a.authenticate_wire_batch(texts)
+            times[name].append(time.perf_counter() - t0)
+            breakdown[name].append(dict(a._g.last_wire_breakdown))
+        assert res["gpu_idents"] == res["host_idents"], "results differ between the identifier passes"
+        assert all(r.__class__ is str for r in res["gpu_idents"]), "a request of the all-valid batch failed"
+        del res
+    assert all(a.stats["wire_host_items"] == 0 for a in auth.values()), "the wire scan left items to the host"
+    out = {"n": args.n, "signers": args.signers, "batches": args.batches}
+    for name in auth:
+        ts = [t * 1e3 for t in times[name]]
+        out[name] = {"batch_ms": {"p50": round(statistics.median(ts), 3), "min": round(min(ts), 3),
+                                  "max": round(max(ts), 3)}}
+        for k in phases:
+            v = [b[k] for b in breakdown[name]]
+            out[name][k + "_ms"] = {"p50": round(statistics.median(v), 3), "min": round(min(v), 3),
+                                    "max": round(max(v), 3)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -66,6 +111,7 @@ def main():
     ap.add_argument("--batches", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--write-corpus", default=None)
+    ap.add_argument("--idents-ab", action="store_true")
     args = ap.parse_args()
     if args.write_corpus:
         return write_corpus(args.write_corpus)
@@ -76,6 +122,16 @@ def main():
     texts, dicts, idrs, vks = build(eng, args.n, args.signers, args.alias_len)
     print("built %d requests, %.0f B mean text, in %.1f s" % (
         args.n, sum(len(t) for t in texts[:1000]) / min(args.n, 1000), time.perf_counter() - t0), flush=True)
+    if args.idents_ab:
+        del dicts
+        line = json.dumps(idents_ab(eng, args, texts, idrs, vks))
+        print(line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        eng.close()
+        return
     a = GpuAuthNr(engine=eng)
     for idr, vk in zip(idrs, vks):
         a.addIdr(idr, vk)
