@@ -320,9 +320,9 @@ __global__ __launch_bounds__(kBlsBlock) void edv_bls_verify_quad_kernel(const ui
 // 16-18.  Per step each lane reads its operation
 // (prefetched two steps ahead) and its operand slots, and writes its result after a barrier
 // (for a one-wave block the barrier is only the compiler's fence: LDS is in order per wave).
-// verdict[i]: 1 accept, 0 reject, 2 redo on the four-lane kernel (a degenerate Miller step
+// verdict[i]: 1 accept, 0 reject, 2 redo on a lane-per-check kernel (a degenerate Miller step
 // flagged by the program, or no point among the 61 candidates -- about 2^-61 of messages, so no
-// message can be searched for that costs its round the four-lane kernel: bn254.h's branches decide).
+// message can be searched for that costs its round that second kernel: bn254.h's branches decide).
 constexpr int kHashTries = 16;  // candidates on lanes 0..15; lanes kHashTries..+2 decode; 45 more after
 __device__ __forceinline__ bool hash_lane(int lane) { return lane < kHashTries || lane >= kHashTries + 3; }
 __device__ __forceinline__ int hash_candidate(int lane) { return lane < kHashTries ? lane : lane - 3; }
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(kBlsBlock) void edv_bls_verify_wave_kernel(const ui
       x[k] = (uint32_t)t;
       c = t >> 32;
     }
-    while (fp_geq_p(x)) {  // mod p (h < 2^256 < 5p)
+    while (fp_geq_p(x)) {  // mod p (h < 2^256 < 7p: up to six rounds)
       fp t;
       fp_reduce_once(t, x);
 #pragma unroll
@@ -658,8 +658,9 @@ static int bls_verify(edv_ctx* ctx, const uint8_t* sig128, const uint8_t* msgs, 
     }
     if (redo.empty()) return 0;
     // the checks the wave form could not decide (no point among H(m)'s first candidates -- a message
-    // can be searched for that --, a degenerate Miller step): only they, compacted, on the four-lane
-    // kernel (one crafted message no longer re-runs its whole COMMIT round)
+    // can be searched for that --, a degenerate Miller step): only they, compacted from the caller's
+    // own (unrebased) arrays, on whichever of the four-, two- and one-lane kernels the pair limit
+    // selects for their number (one crafted message no longer re-runs its whole COMMIT round)
     const uint64_t m = redo.size();
     std::vector<uint8_t> rs(128 * m), rmsg, rvk;
     std::vector<uint64_t> roff(m + 1, 0), rvoff;

@@ -896,7 +896,7 @@ EDV_BN_NI void g1_hash(g1& r, const uint8_t* msg, uint64_t mlen) {
     uint32_t x[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) x[k] = h[k];
-    while (fp_geq_p(x)) {  // h mod p (h < 2^256 < 5p)
+    while (fp_geq_p(x)) {  // h mod p (h < 2^256 < 7p: up to six rounds)
       fp t;
       fp_reduce_once(t, x);
 #pragma unroll

@@ -479,6 +479,69 @@ int edv_host_bls_verify_program(const uint8_t sig128[128], const uint8_t* msg, u
   if (flag) return 2;
   return blsp_result_is_one(S) ? 1 : 0;
 }
+
+// create_multi_sig over wire bytes: the sum of n G1 points (edv_bls_aggregate_kernel's loop)
+void edv_host_bls_aggregate(const uint8_t* sig128, uint64_t n, uint8_t out128[128]) {
+  using namespace edv::bn;
+  g1 acc;
+  g1_inf(acc);
+  for (uint64_t k = 0; k < n; ++k) {
+    g1 t;
+    g1_from_bytes(t, sig128 + 128 * k);
+    g1_add(acc, acc, t);
+  }
+  g1_to_bytes(out128, acc);
+}
+
+// The CPU twins of tests/native/bls_fp_probe.hip (same signatures): the Fp primitives on raw
+// 8-limb values below p, and single program operations over a slot table.
+// op: 0 fp_add, 1 fp_sub, 2 fp_neg, 3 fp_dbl, 4 fp_mul, 5 fp_inv_plain_vt (neg, dbl, inv: of a)
+int edv_host_bn_fp(int op, const uint32_t* a, const uint32_t* b, uint64_t n, uint32_t* out) {
+  using namespace edv::bn;
+  if (op < 0 || op > 5) return -1;
+  for (uint64_t i = 0; i < n; ++i) {
+    fp x, y, r;
+    fp_load(x, a + 8 * i);
+    fp_load(y, b + 8 * i);
+    switch (op) {
+      case 0: fp_add(r, x, y); break;
+      case 1: fp_sub(r, x, y); break;
+      case 2: fp_neg(r, x); break;
+      case 3: fp_dbl(r, x); break;
+      case 4: fp_mul(r, x, y); break;
+      default: fp_inv_plain_vt(r.v, x.v); break;
+    }
+    for (int k = 0; k < 8; ++k) out[8 * i + k] = r.v[k];
+  }
+  return 0;
+}
+// ops: n_ops x kOpWords words; slots: n_slots x 8 limbs (read only); per operation out (8 limbs,
+// zero when nothing is written), wrote (blsp_exec's return) and flag.  -1: a field names a slot
+// past the table.
+int edv_host_blsp_exec(const uint32_t* ops, uint64_t n_ops, const uint32_t* slots, uint64_t n_slots, uint32_t* out,
+                       uint8_t* wrote, uint32_t* flag) {
+  using namespace edv::bn;
+  namespace P = edv::blsp;
+  for (uint64_t i = 0; i < n_ops; ++i)
+    for (int f = 0; f <= P::kMaxTerms; ++f)
+      if (blsp_field(ops + P::kOpWords * i, f) >= n_slots) return -1;
+  const fp* S = (const fp*)slots;
+  for (uint64_t i = 0; i < n_ops; ++i) {
+    fp r;
+    fp_zero(r);
+    uint32_t fl = 0;
+    wrote[i] = blsp_exec(ops + P::kOpWords * i, S, r, &fl) ? 1 : 0;
+    flag[i] = fl;
+    for (int k = 0; k < 8; ++k) out[8 * i + k] = r.v[k];
+  }
+  return 0;
+}
+// kOpWords, kMaxTerms, then the kind codes kNop, kMul, kInv, kZchk, kLin
+void edv_host_blsp_layout(uint32_t out[7]) {
+  namespace P = edv::blsp;
+  const uint32_t v[7] = {(uint32_t)P::kOpWords, (uint32_t)P::kMaxTerms, P::kNop, P::kMul, P::kInv, P::kZchk, P::kLin};
+  for (int k = 0; k < 7; ++k) out[k] = v[k];
+}
 }  // extern "C"
 
 // ---- the wire scanner (wire_scan.h, the code of edv_wire_scan_kernel's lanes) on the CPU, every

@@ -16,9 +16,9 @@ machine, so their published algorithm is restated here:
     ECP::new_big: x = h mod p, y = (x^3+2)^((p+1)/4) when x^3+2 is a square,
     else h += 1 and retry.
   * G2 bytes (128): x.a | x.b | y.a | y.b, 32-byte big-endian each (AMCL
-    ECP2::tobytes); a decoding that is not on the curve is the point at
-    infinity.  G1 bytes (128): 0x04 | x | y | 63 zero bytes (ECP::tobytes
-    into indy-crypto's 128-byte buffer); a first byte other than 0x04 takes
+    ECP2::tobytes); a decoding that is not on the curve, or has a coordinate
+    >= p, is the point at infinity.  G1 bytes (128): 0x04 | x | y | 63 zero
+    bytes (ECP::tobytes into indy-crypto's 128-byte buffer); a first byte other than 0x04 takes
     y = sqrt(x^3+2) (ECP::new_big); off-curve or x, y >= p is infinity.
   * the pairing: the reduced optimal ate pairing of BN curves, loop |6x+2|,
     conjugation for x < 0, then the lines through pi(Q) and -pi^2(Q).
@@ -251,9 +251,13 @@ def b58encode(b):
 
 
 def g2_from_bytes(b):
-    """AMCL ECP2::frombytes: x.a | x.b | y.a | y.b big-endian; off curve -> infinity."""
+    """AMCL ECP2::frombytes: x.a | x.b | y.a | y.b big-endian; off curve -> infinity.
+    A coordinate >= p is infinity too, as for G1 and as bn254.h's g2_from_bytes decodes it (the
+    product's policy: one byte string per verkey; F2() would otherwise reduce it silently)."""
     assert len(b) == 128
     v = [int.from_bytes(b[32 * k:32 * k + 32], "big") for k in range(4)]
+    if any(c >= P for c in v):
+        return None
     pt = (F2(v[0], v[1]), F2(v[2], v[3]))
     return pt if g2_on_curve(pt) else None
 
@@ -387,8 +391,11 @@ def generator():
     return g2_from_bytes(b58decode(G2_GEN_B58))
 
 
-def keygen(sk, gen=None):
-    return g2_mul(gen or generator(), sk % R)
+DEFAULT_GEN = "the reference's generator"  # keygen's and verify's default; None is a generator at infinity
+
+
+def keygen(sk, gen=DEFAULT_GEN):
+    return g2_mul(generator() if gen is DEFAULT_GEN else gen, sk % R)
 
 
 def sign(msg, sk):
@@ -402,19 +409,20 @@ def aggregate(sigs):
     return acc
 
 
-def verify(sig, msg, vk, gen=None):
+def verify(sig, msg, vk, gen=DEFAULT_GEN):
     """Bls.verify: e(sig, g) == e(H(m), vk).  A signature, verkey (sum) or
     generator at infinity is rejected (the product's policy, bn254.h
     bls_check: 1 == 1 would accept a forged multi-signature with no
     participants; AMCL's own answer for these inputs is unpinned)."""
-    gen = gen or generator()
+    if gen is DEFAULT_GEN:
+        gen = generator()
     if sig is None or vk is None or gen is None:
         return False
     lhs = final_exp(miller_loop(sig, gen) * miller_loop(g1_neg(hash_to_g1(msg)), vk))
     return lhs.isone()
 
 
-def verify_multi(msig, msg, vks, gen=None):
+def verify_multi(msig, msg, vks, gen=DEFAULT_GEN):
     """Bls.verify_multi_sig: the verkeys are summed, then verify."""
     acc = None
     for v in vks:
@@ -427,6 +435,11 @@ def verify_bytes(sig128, msg, vk128, gen128=None):
     checked the lengths: 32 or 128)."""
     gen = g2_from_bytes(gen128) if gen128 else generator()
     return verify(g1_from_bytes(sig128), msg, g2_from_bytes(vk128), gen)
+
+
+def verify_multi_bytes(msig128, msg, vk128s, gen128):
+    """verify_multi_sig over the wire bytes, every value decoded here."""
+    return verify_multi(g1_from_bytes(msig128), msg, [g2_from_bytes(v) for v in vk128s], g2_from_bytes(gen128))
 
 
 def f12_to_tower(f):
