@@ -39,8 +39,9 @@
  * (edv_set_options checks every field before applying any; the authenticator
  * never changes them); measurements are one edv_stats struct.  DIAGNOSTIC
  * (benches and tests, not the drop-in): edv_get_stats, the *_device forms,
- * the synthetic-load signer (edv_seed_keypair_batch, edv_sign_*), and
- * edv_bls_sign_batch / edv_bls_keygen_batch.  tests/test_abi.py fails on any
+ * the synthetic-load signer (edv_seed_keypair_batch, edv_sign_*),
+ * edv_bls_sign_batch / edv_bls_keygen_batch, and the read-backs
+ * (edv_wire_readback, edv_comb_table_read).  tests/test_abi.py fails on any
  * exported edv_* symbol this header does not declare.
  */
 #ifndef PLENUM_EDVERIFY_H
@@ -226,6 +227,16 @@ int edv_keys_reset(edv_ctx *ctx);
  * context default).  Only with no keys registered; frees the key store. */
 int edv_keys_set_window(edv_ctx *ctx, int w);
 int edv_keys_window(edv_ctx *ctx);
+/* DIAGNOSTIC: read comb table entries back as the verify kernels find them, so tests check every
+ * entry and not only verdicts.  Entries [first, first + count) of row `row` of registered key
+ * key_id's table of -A, or of the base point's table (W = edv_base_window()) for key_id = -1, go to
+ * out[count * 32] as stored: the 30 limb words of (y+x, y-x, 2dxy) of (j+1) * 2^(W*row) * P for
+ * entry j, then 2 pad words.  A key's row has 2^(W-1) entries at W = edv_keys_window() and lies at
+ * (row * capacity + key_id) * 2^(W-1) entries of the row-major store.  Synchronous host-pointer
+ * call; waits for queued key builds (as edv_keys_sync) first.  EDV_EINVAL, with out untouched and
+ * nothing read, for a row at or beyond the table's rows, first + count beyond the row's entries,
+ * count = 0 (also at first = the row's entry count), a key_id >= edv_keys_count() or < -1. */
+int edv_comb_table_read(edv_ctx *ctx, int64_t key_id, uint32_t row, uint64_t first, uint64_t count, uint32_t *out);
 
 /* Verify against registered keys: item i uses key id key_idx[i] (uint32);
  * an id >= edv_keys_count() is rejected (never read out of bounds).

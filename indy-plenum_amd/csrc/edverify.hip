@@ -863,8 +863,8 @@ __global__ __launch_bounds__(kSortThreads) void edv_key_scatter_kernel(const uin
 
 // ---- key-table path (comb.h) ---------------------------------------------
 // Registered keys: comb tables of -A at the context's key window (EDV_KEY_WINDOWS).
-// Base point: W = 8 comb table (512 KiB) built once per context by the same
-// kernels.
+// Base point: the kBaseW comb table (W = 24: 11 rows x 2^23 entries, 11 GiB) built once per
+// context by the same kernels.
 #ifndef EDV_COMB_MIN_WAVES
 #define EDV_COMB_MIN_WAVES 4  // 128 VGPRs: 1M lanes = 3.8 rounds of 262k (3 waves: 5.1 rounds -> 15% tail); -11% vs 3 (tools/ab_keyed.py)
 #endif
@@ -3947,6 +3947,37 @@ int edv_wire_readback(edv_ctx* ctx, uint8_t* sig64, uint8_t* msgs, uint32_t* msg
   return 0;
 }
 
+int edv_comb_table_read(edv_ctx* ctx, int64_t key_id, uint32_t row, uint64_t first, uint64_t count, uint32_t* out) {
+  int r = set_device(ctx);
+  if (r) return r;
+  if (!out) return set_err(EDV_EINVAL, "null pointer");
+  if ((r = edv_keys_sync(ctx))) return r;
+  // the addresses the comb kernels read: DevComb<kBaseW>{d_btab_comb32} and, for a key, the
+  // row-major store (row * key_cap + key) * kEntries
+  uint64_t rows, entries;
+  const uint32_t* src;
+  if (key_id < 0) {
+    if (key_id != -1) return set_err(EDV_EINVAL, "key id %lld (-1 = the base table)", (long long)key_id);
+    rows = Window<kBaseW>::kRows;
+    entries = Window<kBaseW>::kEntries;
+    src = row < rows ? ctx->d_btab_comb32 + (uint64_t)row * entries * kEntryWords : nullptr;
+  } else {
+    if ((uint64_t)key_id >= ctx->key_count)
+      return set_err(EDV_EINVAL, "key id %lld of %llu", (long long)key_id, (unsigned long long)ctx->key_count);
+    rows = key_rows(ctx->key_w);
+    entries = (uint64_t)key_tab_words(ctx->key_w) / rows / kEntryWords;
+    src = row < rows ? ctx->d_key_tab + ((uint64_t)row * ctx->key_cap + (uint64_t)key_id) * entries * kEntryWords : nullptr;
+  }
+  if (row >= rows) return set_err(EDV_EINVAL, "row %u of %llu", row, (unsigned long long)rows);
+  if (count == 0 || first > entries || count > entries - first)
+    return set_err(EDV_EINVAL, "entries [%llu, +%llu) of a row of %llu", (unsigned long long)first,
+                   (unsigned long long)count, (unsigned long long)entries);
+  HIP_TRY(hipMemcpyAsync(out, src + first * kEntryWords, (size_t)count * kEntryWords * 4, hipMemcpyDeviceToHost,
+                         ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 int edv_verify_submit(edv_ctx* ctx, int keyed, const uint8_t* sig, int sig_format, const uint8_t* keys,
                       const uint8_t* msgs, const uint64_t* msg_off, uint64_t n, uint64_t* ticket) {
   int r = set_device(ctx);
@@ -4069,7 +4100,7 @@ edv_ctx* edv_create(int device) {
   if ((e = hipMemcpy(ctx->d_btab_comb, BASE_COMB_U32, sizeof(BASE_COMB_U32), hipMemcpyHostToDevice)) != hipSuccess)
     return fail("hipMemcpy", e);
   {
-    // W = 8 base-point comb table, built on the device by the key-table kernels
+    // the kBaseW base-point comb table (11 GiB at W = 24), built on the device by the key-table kernels
     constexpr int rowsB = Window<kBaseW>::kRows, EB = Window<kBaseW>::kEntries;
     uint32_t *rows = nullptr, *pre = nullptr;
     if ((e = hipMalloc(&ctx->d_btab_comb32, (size_t)kBaseTabWords * 4)) != hipSuccess) return fail("hipMalloc", e);

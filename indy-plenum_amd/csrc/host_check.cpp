@@ -229,14 +229,25 @@ int edv_host_is_canonical_point(const uint8_t s[32]) {
 // The key-table (comb) path on the CPU: build the W-window table of -A and
 // the W = 8 table of B with the device code, then [h](-A) + [S]B by the comb
 // (comb_mul_add, the kernel's code).  Result point and the combined prechecks.
+// The key's table, kept from call to call while the key stays the same (per thread and window).
+template <int W>
+static const std::vector<uint32_t>& key_table(const uint32_t pk[8], const ge_p3& A) {
+  thread_local std::vector<uint32_t> tab;
+  thread_local uint32_t have[8];
+  if (tab.empty() || memcmp(have, pk, 32) != 0) {
+    build_table<W>(tab, A);
+    memcpy(have, pk, 32);
+  }
+  return tab;
+}
+
 template <int W>
 static bool comb_point(ge_p3& Q, const uint32_t sig[16], const uint32_t pk[8], const uint8_t* msg, uint64_t mlen) {
   uint32_t h[8];
   bool ok = verify_phase_hash(h, sig, pk, msg, mlen);
   ge_p3 A;
   ok = ge_frombytes(A, pk, true) && is_canonical_point(pk) && !has_small_order(pk) && ok;
-  std::vector<uint32_t> atab;
-  build_table<W>(atab, A);
+  const std::vector<uint32_t>& atab = key_table<W>(pk, A);
   comb_mul_set<W>(Q, h, HostComb<W>{atab.data()});
   comb_mul_add<kBaseW>(Q, sig + 8, HostComb<kBaseW>{base_comb()});
   return ok;
@@ -253,6 +264,8 @@ static bool comb_point_w(int w, ge_p3& Q, const uint32_t sig[16], const uint32_t
     case 10: return comb_point<10>(Q, sig, pk, msg, mlen);
     case 11: return comb_point<11>(Q, sig, pk, msg, mlen);
     case 12: return comb_point<12>(Q, sig, pk, msg, mlen);
+    case 14: return comb_point<14>(Q, sig, pk, msg, mlen);
+    case 16: return comb_point<16>(Q, sig, pk, msg, mlen);
     default: return comb_point<8>(Q, sig, pk, msg, mlen);
   }
 }
@@ -275,31 +288,65 @@ int edv_host_verify_comb(const uint8_t* sig64, const uint8_t* pk32, const uint8_
 }  // extern "C"
 
 template <int W>
-static int digits_w(const uint32_t x[8], int* out) {
-  uint32_t y[9];
-  comb_recode<W>(y, x);
-  for (int r = 0; r < Window<W>::kRows; ++r) out[r] = comb_digit<W>(y, r);
+static int digits_w(const uint32_t x[8], int* out, bool by_next) {
+  if (by_next) {  // the batch kernels' routine: funnel shifts, one digit per call
+    CombDigits<W> dg(x);
+    for (int r = 0; r < Window<W>::kRows; ++r) out[r] = dg.next();
+  } else {
+    uint32_t y[9];
+    comb_recode<W>(y, x);
+    for (int r = 0; r < Window<W>::kRows; ++r) out[r] = comb_digit<W>(y, r);
+  }
   return Window<W>::kRows;
+}
+
+#define EDV_HOST_WINDOWS(X) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(24)
+
+static int digits_any(const uint8_t x32[32], int w, int* out, bool by_next) {
+  uint32_t x[8];
+  memcpy(x, x32, 32);
+  switch (w) {
+#define EDV_HOST_DIGITS(W) \
+  case W: return digits_w<W>(x, out, by_next);
+    EDV_HOST_WINDOWS(EDV_HOST_DIGITS)
+#undef EDV_HOST_DIGITS
+    default: return -1;
+  }
+}
+
+template <int W>
+static int64_t table_w(const ge_p3& P, uint32_t* out) {
+  if (out) {
+    std::vector<uint32_t> tab;
+    build_table<W>(tab, P);
+    memcpy(out, tab.data(), tab.size() * 4);
+  }
+  return (int64_t)Window<W>::kTableWords;
 }
 
 extern "C" {
 
-// comb.h signed radix-2^W digits of a 32-byte scalar; returns the row count.
-int edv_host_comb_digits(const uint8_t x32[32], int w, int* out) {
-  uint32_t x[8];
-  memcpy(x, x32, 32);
+// comb.h signed radix-2^W digits of a 32-byte scalar (W = 4..16 and 24) through comb_digit (the
+// small and resident kernels' routine); returns the row count, -1 for another W.
+int edv_host_comb_digits(const uint8_t x32[32], int w, int* out) { return digits_any(x32, w, out, false); }
+// The same digits through CombDigits<W>::next() (the batch kernels' routine).
+int edv_host_comb_digits_next(const uint8_t x32[32], int w, int* out) { return digits_any(x32, w, out, true); }
+
+// The comb table of the point pk32 encodes (negate != 0: of its negative, as the key store holds
+// -A) at window w <= 16, built by build_table<W> -- comb_rows and comb_fill_strided lane by lane, as
+// edv_key_rows_kernel / edv_comb_fill_kernel run them -- in comb.h's layout (row-major: row r's
+// entries at r * 2^(w-1)).  Returns the table's word count (out may be null to ask for it only);
+// -1 for another w or an encoding that is not on the curve.
+int64_t edv_host_comb_table(const uint8_t pk32[32], int negate, int w, uint32_t* out) {
+  uint32_t pk[8];
+  memcpy(pk, pk32, 32);
+  ge_p3 P;
+  if (w < 4 || w > 16 || !ge_frombytes(P, pk, negate != 0)) return -1;
   switch (w) {
-    case 4: return digits_w<4>(x, out);
-    case 5: return digits_w<5>(x, out);
-    case 6: return digits_w<6>(x, out);
-    case 7: return digits_w<7>(x, out);
-    case 8: return digits_w<8>(x, out);
-    case 9: return digits_w<9>(x, out);
-    case 10: return digits_w<10>(x, out);
-    case 11: return digits_w<11>(x, out);
-    case 12: return digits_w<12>(x, out);
-    case 13: return digits_w<13>(x, out);
-    case 14: return digits_w<14>(x, out);
+#define EDV_HOST_TABLE(W) \
+  case W: return W <= 16 ? table_w<(W <= 16 ? W : 16)>(P, out) : -1;
+    EDV_HOST_WINDOWS(EDV_HOST_TABLE)
+#undef EDV_HOST_TABLE
     default: return -1;
   }
 }

@@ -54,6 +54,7 @@ SIGNATURES = {
     "edv_keys_reset": (_I, [_P]),
     "edv_keys_set_window": (_I, [_P, _I]),
     "edv_keys_window": (_I, [_P]),
+    "edv_comb_table_read": (_I, [_P, _c.c_int64, _U32, _U64, _U64, _P]),
     "edv_verify_batch_keyed": (_I, [_P, _P, _P, _P, _P, _U64, _P]),
     "edv_verify_batch_keyed_device": (_I, [_P, _P, _P, _P, _P, _U64, _P, _P]),
     "edv_verify_one": (_I, [_P, _P, _U32, _P, _U64, _P]),

@@ -670,6 +670,18 @@ class EdVerifyEngine:
     def keys_count(self):
         return int(self._lib.edv_keys_count(self._ctx))
 
+    def comb_table_read(self, key_id, row, first, count, out=None):
+        """DIAGNOSTIC (edv_comb_table_read): entries [first, first + count) of row `row` of
+        registered key key_id's comb table of -A (key_id = -1: the base point's table) as
+        uint32[count, 32]: 30 limb words of (y+x, y-x, 2dxy) and 2 pad words each, as stored.
+        `out` (a C-contiguous uint32 array of count * 32 words) is filled in place when given."""
+        if out is None:
+            out = np.empty((int(count), 32), dtype=np.uint32)
+        elif out.dtype != np.uint32 or not out.flags.c_contiguous or out.size != int(count) * 32:
+            raise ValueError("out must be a contiguous uint32 array of count * 32 words")
+        check(self._lib.edv_comb_table_read(self._ctx, int(key_id), int(row), int(first), int(count), _ptr(out)))
+        return out
+
     keys_generation = 0  # bumped by keys_reset: a KeyStore (keystore.py) drops its ids
 
     def keys_reset(self):

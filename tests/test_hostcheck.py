@@ -203,7 +203,12 @@ def test_kernel_batch_encode(hostcheck):
 def test_comb_recoding_exact_up_to_L():
     """Signed radix-2^W digits (comb.h) reconstruct every scalar below L,
     including the top of the range where x + bias needs W*rows >= 254 bits
-    (W = 11 with 23 rows would overflow there), and stay in table range."""
+    (W = 11 with 23 rows would overflow there), and stay in table range: at every
+    window the key store accepts (4 to 16) and the shipped base window (24), through
+    comb_digit (the small and resident kernels) and through CombDigits::next() (the batch
+    kernels' funnel shifts), which must agree.  Scalars: the range's edges, random ones,
+    every S and h of the digit-edge fixture, and for each row the scalars whose digit
+    field in that row alone is all zeros or all ones."""
     import ctypes as C
     from conftest import PKG
     import os
@@ -211,14 +216,35 @@ def test_comb_recoding_exact_up_to_L():
     rng = random.Random(11)
     xs = [0, 1, L - 1, L - 2, 2**252, 2**252 - 1, L - 2**200] + [rng.randrange(L) for _ in range(300)]
     xs += [L - 1 - rng.randrange(2**128) for _ in range(100)]
-    for w in range(4, 15):
-        out = (C.c_int * 80)()
-        for x in xs:
-            rows = lib.edv_host_comb_digits(x.to_bytes(32, "little"), w, out)
-            assert rows == -(-254 // w)
+    d = load_npz("comb_digit_edge.npz")
+    for sig, pk, msg, expect in items_of(d):
+        if expect:
+            xs.append(int.from_bytes(sig[32:], "little"))
+            xs.append(int.from_bytes(hashlib.sha512(sig[:32] + pk + msg).digest(), "little") % L)
+    for w in list(range(4, 17)) + [24]:
+        rows, half = -(-254 // w), 1 << (w - 1)
+        edge = []
+        for i in range(rows):  # digit i = -2^(w-1) (field 0) or 2^(w-1) - 1 (field all ones), the others 0 or one 1
+            for v in (-half, half - 1):
+                for carry in (0, 1):
+                    x = (v << (w * i)) + (carry << (w * (i + 1)) if i + 1 < rows else 0)
+                    if 0 <= x < L:
+                        edge.append((x, i, v))
+        assert {(i, v) for _, i, v in edge} >= {(i, v) for i in range(rows - 2) for v in (-half, half - 1)}
+        out, out2 = (C.c_int * 80)(), (C.c_int * 80)()
+        for x, i, v in [(x, None, None) for x in xs] + edge:
+            got_rows = lib.edv_host_comb_digits(x.to_bytes(32, "little"), w, out)
+            assert got_rows == rows
+            assert lib.edv_host_comb_digits_next(x.to_bytes(32, "little"), w, out2) == rows
             d = list(out[:rows])
-            assert all(-(1 << (w - 1)) <= v < (1 << (w - 1)) for v in d), (w, x)
-            assert sum(v << (w * i) for i, v in enumerate(d)) == x, (w, hex(x))
+            assert d == list(out2[:rows]), (w, hex(x))
+            assert all(-half <= t < half for t in d), (w, x)
+            assert sum(t << (w * k) for k, t in enumerate(d)) == x, (w, hex(x))
+            y = x + sum(half << (w * k) for k in range(rows))
+            assert d == [((y >> (w * k)) & (2 * half - 1)) - half for k in range(rows)], (w, hex(x))
+            if i is not None:
+                assert d[i] == v, (w, i, v)
+    assert lib.edv_host_comb_digits(bytes(32), 17, out) == -1
 
 
 def test_kernel_sha256_any_alignment(hostcheck):
