@@ -23,14 +23,9 @@
 
 namespace edv {
 
-// Product form of the encode (fe_mul_o ORDER).  It runs at about one wave
-// per SIMD (M results per lane), but ten independent accumulator chains per
-// product (ORDER 1) measured slower than the carry-serial chains (ORDER 2):
+// The encode runs at about one wave per SIMD (M results per lane), yet ten independent
+// accumulator chains per product measured slower than fe_mul's carry-serial chains:
 // encode 0.148-0.152 -> 0.161-0.166 ms per 1M (profiles/r02o/ab_enc).
-#ifndef EDV_ENCODE_ORDER
-#define EDV_ENCODE_ORDER 2
-#endif
-
 template <int M, class A>
 EDV_HD void encode_batch(A& a) {
   uint32_t zero_mask = 0;
@@ -48,21 +43,21 @@ EDV_HD void encode_batch(A& a) {
     if (j == 0)
       acc = z;
     else
-      fe_mul_o<EDV_ENCODE_ORDER>(acc, acc, z);
+      fe_mul_chain(acc, acc, z);
     a.put_pre(j, acc);
   }
   fe inv;
-  fe_invert<EDV_ENCODE_ORDER>(inv, acc);
+  fe_invert(inv, acc);
 #pragma unroll 1
   for (int j = M - 1; j >= 0; --j) {
     fe zinv;
     if (j > 0) {
       fe prev;
       a.get_pre(j - 1, prev);
-      fe_mul_o<EDV_ENCODE_ORDER>(zinv, inv, prev);
+      fe_mul_chain(zinv, inv, prev);
       fe_1(z);
       if (a.valid(j) && !((zero_mask >> j) & 1u)) a.z(j, z);
-      fe_mul_o<EDV_ENCODE_ORDER>(inv, inv, z);
+      fe_mul_chain(inv, inv, z);
     } else {
       zinv = inv;
     }
@@ -70,8 +65,8 @@ EDV_HD void encode_batch(A& a) {
     fe_1(X);
     fe_1(Y);
     if (a.valid(j)) a.xy(j, X, Y);
-    fe_mul_o<EDV_ENCODE_ORDER>(x, X, zinv);
-    fe_mul_o<EDV_ENCODE_ORDER>(y, Y, zinv);
+    fe_mul_chain(x, X, zinv);
+    fe_mul_chain(y, Y, zinv);
     uint32_t enc[8];
     fe_tobytes(enc, y);
     enc[7] ^= fe_isnegative(x) << 31;

@@ -99,21 +99,15 @@ EDV_HD int comb_digit(const uint32_t y[9], int i) {
 
 // Signed-digit entry of row `row` for digit e: T::load(row, j, ge_niels&)
 // gives entry j (= (j+1) * 2^(W*row) * P), or the identity for j = -1 (an
-// address select in the accessors, so no data is shuffled); the sign is
-// applied by ge_madd_signed on Q's side.  A conditional swap of whole fe
-// structs is lowered through scratch memory, so none is done here.
+// address select in the accessors, so no data is shuffled); comb_apply applies
+// the sign.  A conditional swap of whole fe structs is lowered through scratch
+// memory, so none is done here.
 template <class T>
 EDV_HD void comb_fetch(ge_niels& nb, int e, const T& tab, int row) {
   const int m = e < 0 ? -e : e;
   tab.load(row, m - 1, nb);
 }
-#ifndef EDV_SIGNED_MADD
-#define EDV_SIGNED_MADD 0  // 1: fold the sign into ge_madd_signed (p side) instead of selecting the entry
-#endif
 EDV_HD void comb_apply(ge_p3& Q, ge_niels& nb, int e) {
-#if EDV_SIGNED_MADD
-  ge_madd_signed(Q, Q, nb, e < 0);
-#else
   // -entry = (y-x, y+x, -2dxy): per-limb selects in place (no struct swap)
   const bool neg = e < 0;
 #pragma unroll
@@ -126,7 +120,6 @@ EDV_HD void comb_apply(ge_p3& Q, ge_niels& nb, int e) {
   ge_p1p1 u;
   ge_madd(u, Q, nb);
   ge_p1p1_to_p3_addlike(Q, u);
-#endif
 }
 
 // The identity as a niels entry (y+x, y-x, 2dxy) = (1, 1, 0), padded to kEntryWords.
@@ -137,55 +130,10 @@ __device__ __constant__ const uint32_t kNielsIdentity[kEntryWords] = {1, 0, 0, 0
 static const uint32_t kNielsIdentityHost[kEntryWords] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 // Q += [x]P for x < 2^253 by the comb over P's table: kRows mixed additions
-// (7 multiplications each).  Row r + 1's entry is fetched before row r's
-// addition runs, so the table gather overlaps the arithmetic.
-#ifndef EDV_COMB_PREFETCH
-#define EDV_COMB_PREFETCH 0  // 0: none (best: the comb is VALU-bound); 1: row r+1 into registers (spills); 2: touch its line (-5%)
-#endif
-// T::touch(row, j) (optional prefetch): a 4-byte load of entry j's 128-B line
-// whose value is folded into `sink` one row later, so the line is in L2/MALL
-// when the row's own loads arrive and no wait is placed early.
+// (7 multiplications each).  No prefetch of row r + 1: the comb is VALU-bound.
 template <int W, class T>
-EDV_HD uint32_t comb_mul_add(ge_p3& Q, const uint32_t x[8], const T& tab) {
+EDV_HD void comb_mul_add(ge_p3& Q, const uint32_t x[8], const T& tab) {
   CombDigits<W> dg(x);
-  uint32_t sink = 0;
-#if EDV_COMB_PREFETCH == 1
-  int e = dg.next();
-  ge_niels cur;
-  comb_fetch(cur, e, tab, 0);
-#pragma unroll 1
-  for (int r = 0; r < Window<W>::kRows; ++r) {
-    ge_niels next;
-    int e_next = 0;
-    if (r + 1 < Window<W>::kRows) {
-      e_next = dg.next();
-      comb_fetch(next, e_next, tab, r + 1);
-    } else {
-      ge_niels_0(next);
-    }
-    comb_apply(Q, cur, e);
-    cur = next;
-    e = e_next;
-  }
-#elif EDV_COMB_PREFETCH == 2
-  int e = dg.next();
-  uint32_t pf = 0;
-#pragma unroll 1
-  for (int r = 0; r < Window<W>::kRows; ++r) {
-    sink ^= pf;
-    int e_next = 0;
-    if (r + 1 < Window<W>::kRows) {
-      e_next = dg.next();
-      const int m = e_next < 0 ? -e_next : e_next;
-      pf = tab.touch(r + 1, m - 1);
-    }
-    ge_niels nb;
-    comb_fetch(nb, e, tab, r);
-    comb_apply(Q, nb, e);
-    e = e_next;
-  }
-  sink ^= pf;
-#else
 #pragma unroll 1
   for (int r = 0; r < Window<W>::kRows; ++r) {
     const int e = dg.next();
@@ -193,8 +141,6 @@ EDV_HD uint32_t comb_mul_add(ge_p3& Q, const uint32_t x[8], const T& tab) {
     comb_fetch(nb, e, tab, r);
     comb_apply(Q, nb, e);  // nb is consumed
   }
-#endif
-  return sink;
 }
 
 // Q = signed entry e of row 0 as an extended point (Q += entry from the
@@ -202,7 +148,6 @@ EDV_HD uint32_t comb_mul_add(ge_p3& Q, const uint32_t x[8], const T& tab) {
 // 2y, Z = 2, T = XY / Z = 2xy = 2dxy / d -- one multiplication instead of 7.
 // -entry = (y-x, y+x, -2dxy) gives (-2x, 2y, 2, -2xy); the identity entry
 // (1, 1, 0) gives (0, 2, 2, 0).  Output classes: X, Y, Z, T all C.
-template <int ORDER = EDV_FE_MUL_ORDER>
 EDV_HD void comb_set_entry(ge_p3& Q, const ge_niels& nb, int e) {
   const bool neg = e < 0;
   fe p, m, t;
@@ -218,7 +163,7 @@ EDV_HD void comb_set_entry(ge_p3& Q, const ge_niels& nb, int e) {
   fe_carry(Q.Y);
   fe_0(Q.Z);
   Q.Z.v[0] = 2;
-  fe_mul_o<ORDER>(Q.T, t, fe_const_dinv());
+  fe_mul_chain(Q.T, t, fe_const_dinv());
 }
 template <class T>
 EDV_HD void comb_set(ge_p3& Q, int e, const T& tab) {

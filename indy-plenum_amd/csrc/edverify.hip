@@ -479,9 +479,6 @@ struct DevComb {
     return j >= 0 ? tab + (uint64_t)(uint32_t)row * row_words + (uint32_t)j * kEntryWords : ident;
   }
   __device__ void load(int row, int j, ge_niels& nb) const { load_niels(nb, entry(row, j)); }
-  __device__ uint32_t touch(int row, int j) const {  // comb_mul_add's line prefetch
-    return *(const volatile uint32_t*)entry(row, j);
-  }
 };
 
 #ifndef EDV_DSM_MIN_WAVES
@@ -508,20 +505,18 @@ __global__ __launch_bounds__(kBlock, EDV_DSM_MIN_WAVES) void edv_dsm_kernel(cons
   if (!key_ok[u]) flags[i] = 0;  // the key does not decode: reject (the table is still written, so the ladder runs)
   const DevComb<kBaseW> cb{btab_comb, ident};
   ge_p3 Q;
-  uint32_t sink;
   const int split = split_of(*count, n);
   if (split == 8) {
     const DevTableSplit tas(table, 8ull * u);
-    sink = verify_phase_dsm_split_point<8>(Q, h, S, tas, cb);
+    verify_phase_dsm_split_point<8>(Q, h, S, tas, cb);
   } else if (split == 4) {
     const DevTableSplit tas(table, 4ull * u);
-    sink = verify_phase_dsm_split_point<4>(Q, h, S, tas, cb);
+    verify_phase_dsm_split_point<4>(Q, h, S, tas, cb);
   } else {
     const DevTableA ta(table, (uint64_t)u);
-    sink = verify_phase_dsm_point(Q, h, S, ta, cb);
+    verify_phase_dsm_point(Q, h, S, ta, cb);
   }
   store_point_soa(pt, stride, i, Q);
-  if (sink == 0x9e3779b9u && stride == 0) pt[i] = sink;  // keeps the prefetches live
 }
 
 // Batched encode + compare + ballot.  Lane l of wave v owns requests
@@ -966,85 +961,6 @@ __global__ __launch_bounds__(kBlock, EDV_HASH_MIN_WAVES) void edv_hash_keyed_ker
   flags[i] = ok ? 1 : 0;
 }
 
-#ifndef EDV_COMB_SET
-#define EDV_COMB_SET 1  // 1: the key comb's row 0 by comb_set (1 multiplication, not a 7-multiplication addition)
-#endif
-#ifndef EDV_COMB_LDS
-#define EDV_COMB_LDS 0  // 1: entries gathered one row ahead by LDS-DMA (comb_dual_lds): -3% c1, -10% c2 (r02b A/B)
-#endif
-
-// LDS-DMA gather of one 128-B table entry per lane: 8 global_load_lds_dwordx4,
-// piece k of every lane at lds + k * 1 KiB + lane * 16 B (the DMA's lane-linear
-// destination).  No VGPR holds the entry while it is in flight, so the next
-// row's gather runs under the current row's mixed addition without the
-// register cost of a register prefetch (which spilled at 4 waves / SIMD).
-constexpr int kLdsWaveWords = 8 * 64 * 4;  // 8 KiB per wave
-__device__ __forceinline__ void dma_entry(const uint32_t* src, uint32_t* lds) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 4 * k),
-                                     (__attribute__((address_space(3))) void*)(lds + k * 256), 16, 0, 0);
-}
-__device__ __forceinline__ void lds_entry(ge_niels& nb, const uint32_t* lds, uint32_t lane) {
-  uint32_t w[32];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const uint4 v = *(const uint4*)(lds + k * 256 + lane * 4);
-    w[4 * k] = v.x;
-    w[4 * k + 1] = v.y;
-    w[4 * k + 2] = v.z;
-    w[4 * k + 3] = v.w;
-  }
-#pragma unroll
-  for (int l = 0; l < 10; ++l) {
-    nb.ypx.v[l] = w[l];
-    nb.ymx.v[l] = w[10 + l];
-    nb.xy2d.v[l] = w[20 + l];
-  }
-}
-
-// [h](-A) + [S]B over the key comb (W) and the base comb (kBaseW) as one
-// stream of kRows(W) + kRows(kBaseW) entries: entry s + 1 is DMA'd into the
-// wave's LDS slot right after entry s has been read out of it, so each gather
-// has a whole mixed addition (x 4 waves per SIMD) to land.
-template <int W>
-__device__ void comb_dual_lds(ge_p3& Q, const uint32_t h[8], const uint32_t S[8], const DevComb<W>& ta,
-                              const DevComb<kBaseW>& tb, uint32_t* lds, uint32_t lane) {
-  constexpr int RK = Window<W>::kRows, RB = Window<kBaseW>::kRows;
-  CombDigits<W> dh(h);
-  int e = dh.next();
-  dma_entry(ta.entry(0, (e < 0 ? -e : e) - 1), lds);
-  ge_niels nb;
-  lds_entry(nb, lds, lane);
-  int e_next = dh.next();
-  dma_entry(ta.entry(1, (e_next < 0 ? -e_next : e_next) - 1), lds);
-  comb_set_entry(Q, nb, e);
-#pragma unroll 1
-  for (int r = 1; r < RK; ++r) {
-    e = e_next;
-    lds_entry(nb, lds, lane);
-    if (r + 1 < RK) {
-      e_next = dh.next();
-      dma_entry(ta.entry(r + 1, (e_next < 0 ? -e_next : e_next) - 1), lds);
-    } else {  // the base comb's row 0: digit 0 of S + bias needs only the low word
-      e_next = (int)((S[0] + Window<kBaseW>::bias_word(0)) & ((1u << kBaseW) - 1)) - (1 << (kBaseW - 1));
-      dma_entry(tb.entry(0, (e_next < 0 ? -e_next : e_next) - 1), lds);
-    }
-    comb_apply(Q, nb, e);
-  }
-  CombDigits<kBaseW> ds(S);
-  e_next = ds.next();
-#pragma unroll 1
-  for (int r = 0; r < RB; ++r) {
-    e = e_next;
-    lds_entry(nb, lds, lane);
-    if (r + 1 < RB) {
-      e_next = ds.next();
-      dma_entry(tb.entry(r + 1, (e_next < 0 ? -e_next : e_next) - 1), lds);
-    }
-    comb_apply(Q, nb, e);
-  }
-}
 // [h](-A) + [S]B over the key's comb (W) and the base comb (kBaseW): no doublings.
 template <int W>
 __global__ __launch_bounds__(kBlock, EDV_COMB_MIN_WAVES) void edv_comb_kernel(const uint8_t* __restrict__ sig64,
@@ -1070,20 +986,9 @@ __global__ __launch_bounds__(kBlock, EDV_COMB_MIN_WAVES) void edv_comb_kernel(co
   const DevComb<W> ta{key_tab + (uint64_t)key * kRowWordsW, ident, key_cap * kRowWordsW};  // row-major store
   const DevComb<kBaseW> tb{btab, ident};
   ge_p3 Q;
-#if EDV_COMB_LDS
-  __shared__ uint32_t lds_slots[kBlock / 64][kLdsWaveWords];
-  comb_dual_lds<W>(Q, h, S, ta, tb, lds_slots[threadIdx.x >> 6], threadIdx.x & 63);
-  uint32_t sink = 0;
-#elif EDV_COMB_SET
-  comb_mul_set<W>(Q, h, ta);  // Q = [h](-A): row 0 set, not added to the identity
-  uint32_t sink = comb_mul_add<kBaseW>(Q, S, tb);
-#else
-  ge_p3_0(Q);
-  uint32_t sink = comb_mul_add<W>(Q, h, ta);
-  sink ^= comb_mul_add<kBaseW>(Q, S, tb);
-#endif
+  comb_mul_set<W>(Q, h, ta);  // Q = [h](-A): row 0 set (1 multiplication), not added to the identity (7)
+  comb_mul_add<kBaseW>(Q, S, tb);
   store_point_soa(pt, stride, t, Q);
-  if (sink == 0x9e3779b9u && key0 == 0xffffffffu && key_count == 0) pt[t] = sink;  // keeps the prefetches live
 }
 
 // ---- low-latency keyed verify for small batches (edv_options.small_batch) -------
@@ -1113,14 +1018,6 @@ __device__ __forceinline__ void shfl_fe(fe& out, const fe& in, int delta) {
 // Sum of the p3 points of lanes 0..width-1 of this wave (width a power of two
 // <= 64; lanes >= rows hold the identity) into lane 0: log2(width) levels of
 // p + q (q as cached).
-#ifndef EDV_SMALL_ORDER
-// fe_mul_o order of the small kernel's products.  One wave's serial carry-started chains
-// (2) beat ten independent accumulators (1) here too: R's decode 99.6 vs 118.2 us, the kernel
-// 103.8 vs 123.4 us (tools/small_probe.py, profiles/r05m); and two half-chains joined by a
-// carry ripple (3): decode 107.7 vs 99.0 us (profiles/r05o).
-#define EDV_SMALL_ORDER 2
-#endif
-constexpr int kSO = EDV_SMALL_ORDER;
 __device__ void lane_tree_sum(ge_p3& P, int lane, int width) {
 #pragma unroll 1
   for (int step = 1; step < width; step <<= 1) {
@@ -1132,9 +1029,9 @@ __device__ void lane_tree_sum(ge_p3& P, int lane, int width) {
     if ((lane & (2 * step - 1)) == 0 && lane < width) {
       ge_cached c;
       ge_p1p1 t;
-      ge_p3_to_cached<kSO>(c, Q);
-      ge_add<kSO>(t, P, c);
-      ge_p1p1_to_p3_addlike<kSO>(P, t);
+      ge_p3_to_cached(c, Q);
+      ge_add(t, P, c);
+      ge_p1p1_to_p3_addlike(P, t);
     }
   }
 }
@@ -1144,94 +1041,19 @@ __device__ void comb_row_point(ge_p3& P, const uint32_t y[9], int row, const T& 
   const int e = comb_digit<W>(y, row);
   ge_niels nb;
   tab.load(row, (e < 0 ? -e : e) - 1, nb);
-  comb_set_entry<kSO>(P, nb, e);
+  comb_set_entry(P, nb, e);
 }
 
-// libsodium's frombytes of R (ge_frombytes, negate = false) cut in two at a
-// point of its exponentiation, so the first ~145 products run beside the hash
-// and the rest beside the key comb's tree: part 1 leaves u = y^2 - 1,
-// v = d y^2 + 1, v3 = v^3, t0, t1 and t2 = t1^(2^30) of fe_pow22523(u v^7).
-struct RDecode {
-  fe y, u, v, v3, t0, t1, t2;
-};
-__device__ void r_decode_part1(RDecode& d, const uint32_t s[8]) {
-  fe one, x, z;
-  fe_1(one);
-  fe_frombytes(d.y, s);
-  fe_sq_o<kSO>(d.u, d.y);
-  fe_mul_o<kSO>(d.v, d.u, fe_const_d());
-  fe_sub(d.u, d.u, one);
-  fe_carry(d.u);
-  fe_add(d.v, d.v, one);
-  fe_sq_o<kSO>(d.v3, d.v);
-  fe_mul_o<kSO>(d.v3, d.v3, d.v);
-  fe_sq_o<kSO>(x, d.v3);
-  fe_mul_o<kSO>(x, x, d.v);
-  fe_mul_o<kSO>(z, x, d.u);  // u v^7: fe_pow22523's input, its chain up to t1 = z^(2^100 - 1) then 30 squarings
-  fe_sq_o<kSO>(d.t0, z);
-  fe_sqn<kSO>(d.t1, d.t0, 2);
-  fe_mul_o<kSO>(d.t1, z, d.t1);
-  fe_mul_o<kSO>(d.t0, d.t0, d.t1);
-  fe_sq_o<kSO>(d.t0, d.t0);
-  fe_mul_o<kSO>(d.t0, d.t1, d.t0);
-  fe_sqn<kSO>(d.t1, d.t0, 5);
-  fe_mul_o<kSO>(d.t0, d.t1, d.t0);
-  fe_sqn<kSO>(d.t1, d.t0, 10);
-  fe_mul_o<kSO>(d.t1, d.t1, d.t0);
-  fe_sqn<kSO>(d.t2, d.t1, 20);
-  fe_mul_o<kSO>(d.t1, d.t2, d.t1);
-  fe_sqn<kSO>(d.t1, d.t1, 10);
-  fe_mul_o<kSO>(d.t0, d.t1, d.t0);
-  fe_sqn<kSO>(d.t1, d.t0, 50);
-  fe_mul_o<kSO>(d.t1, d.t1, d.t0);
-  fe_sqn<kSO>(d.t2, d.t1, 30);
-}
-// The rest: x of R with R's sign (false: no square root).  Same value as ge_frombytes.
-__device__ bool r_decode_part2(fe& x, RDecode& d, const uint32_t s[8]) {
-  fe_sqn<kSO>(d.t2, d.t2, 70);
-  fe_mul_o<kSO>(d.t1, d.t2, d.t1);
-  fe_sqn<kSO>(d.t1, d.t1, 50);
-  fe_mul_o<kSO>(d.t0, d.t1, d.t0);
-  fe_sqn<kSO>(d.t0, d.t0, 2);
-  fe z;
-  fe_sq_o<kSO>(x, d.v3);
-  fe_mul_o<kSO>(x, x, d.v);
-  fe_mul_o<kSO>(z, x, d.u);
-  fe_mul_o<kSO>(x, d.t0, z);  // (u v^7)^((p-5)/8)
-  fe_mul_o<kSO>(x, x, d.v3);
-  fe_mul_o<kSO>(x, x, d.u);   // u v^3 (u v^7)^((p-5)/8)
-  fe vxx, chk;
-  fe_sq_o<kSO>(vxx, x);
-  fe_mul_o<kSO>(vxx, vxx, d.v);
-  fe_sub(chk, vxx, d.u);
-  if (!fe_iszero(chk)) {
-    fe_add(chk, vxx, d.u);
-    if (!fe_iszero(chk)) return false;
-    fe_mul_o<kSO>(x, x, fe_const_sqrtm1());
-  }
-  if (fe_isnegative(x) != (s[7] >> 31)) {
-    fe_neg(x, x);
-    fe_carry(x);
-  }
-  return true;
-}
-
-// The same decode with fe_pow22523's chain spread over wave 2's lanes (fe_lanes.h): lane 0 runs
-// the few products before and after it, every lane of the wave the chain.  EDV_SMALL_LANES=0: the
-// one-lane chain above (A/B).
-#ifndef EDV_SMALL_LANES
-#define EDV_SMALL_LANES 1
-#endif
-// EDV_SMALL_DIST_EDGES 1 (default): the products before the chain (u, v, v^3, u v^7) and after it
-// (x, v x^2) distributed too -- ~0.17 us each on the wave against ~0.37 us on lane 0 -- with u - 1
-// formed as u + 2p - 1 and carried back into the dist_* input bounds; 0: on lane 0 (A/B).
-#ifndef EDV_SMALL_DIST_EDGES
-#define EDV_SMALL_DIST_EDGES 1
-#endif
+// libsodium's frombytes of R (ge_frombytes, negate = false) cut in two at a point of its
+// exponentiation, so the first ~145 products run beside the hash and the rest beside the key
+// comb's tree, with fe_pow22523's chain and the few products before and after it (u, v, v^3,
+// u v^7; x, v x^2) spread over wave 2's lanes (fe_lanes.h; ~0.17 us a product on the wave against
+// ~0.37 us on lane 0).  Part 1 leaves u = y^2 - 1 (formed as y^2 + 2p - 1 and carried back into
+// the dist_* input bounds), v = d y^2 + 1, v^3, u v^7, and t0, t1 and t2 = t1^(2^30) of
+// fe_pow22523(u v^7), all distributed (limb k in lane k).
 struct RDecodeL {
-  fe y, u, v, v3, uv7;      // lane 0 (EDV_SMALL_DIST_EDGES 0); y in every lane
-  uint32_t t0, t1, t2;      // distributed (limb k in lane k)
-  uint32_t du, dv, dv3, duv7;  // distributed (EDV_SMALL_DIST_EDGES 1)
+  uint32_t t0, t1, t2;
+  uint32_t du, dv, dv3, duv7;
 };
 // limb k of a lane-uniform fe in lane k (every lane holds f; no cross-lane moves)
 __device__ __forceinline__ uint32_t dist_pick(const fe& f, uint32_t k) {
@@ -1241,45 +1063,22 @@ __device__ __forceinline__ uint32_t dist_pick(const fe& f, uint32_t k) {
   return r;
 }
 __device__ void r_decode_part1_lanes(RDecodeL& d, const uint32_t s[8], uint32_t lane) {
-  fe z;
-  fe_0(z);
-#if EDV_SMALL_DIST_EDGES
   const uint32_t k = lane & 15;
   const LaneTerms sq = c_lane_sq.t[lane], mu = c_lane_mul.t[lane];
-  fe_frombytes(d.y, s);  // (every lane: the same words)
+  fe y;
+  fe_frombytes(y, s);  // (every lane: the same words)
   const bool row0 = lane < 10;
-  const uint32_t yd = dist_form(k < 10 ? dist_pick(d.y, k) : 0u, lane);
+  const uint32_t yd = k < 10 ? dist_pick(y, k) : 0u;
   const uint32_t y2 = dist_sq(yd, sq, lane);
   // v = d y^2 + 1 (limb 0 of a dist_* output < 2^26: the + 1 stays in bounds)
-  const uint32_t dd = dist_form(k < 10 ? dist_pick(fe_const_d(), k) : 0u, lane);
-  d.dv = dist_mul(y2, dd, mu, lane) + dist_form(k == 0 ? 1u : 0u, lane);
+  const uint32_t dd = k < 10 ? dist_pick(fe_const_d(), k) : 0u;
+  d.dv = dist_mul(y2, dd, mu, lane) + (k == 0 ? 1u : 0u);
   // u = y^2 - 1 = y^2 + 2p - 1, carried: limbs of 2p are 2^27 - 38, then 2^26 - 2 / 2^27 - 2
   const uint32_t two_p = k == 0 ? (1u << 27) - 38 : (k & 1) ? (1u << 26) - 2 : (1u << 27) - 2;
   d.du = lane_cols_carry(row0 ? (uint64_t)y2 + two_p - (lane == 0 ? 1u : 0u) : 0ull, lane);
   d.dv3 = dist_mul(dist_sq(d.dv, sq, lane), d.dv, mu, lane);
   d.duv7 = dist_mul(dist_mul(dist_sq(d.dv3, sq, lane), d.dv, mu, lane), d.du, mu, lane);  // u v^7
   const uint32_t zd = d.duv7;
-#else
-  if (lane == 0) {
-    fe one, x;
-    fe_1(one);
-    fe_frombytes(d.y, s);
-    fe_sq_o<kSO>(d.u, d.y);
-    fe_mul_o<kSO>(d.v, d.u, fe_const_d());
-    fe_sub(d.u, d.u, one);
-    fe_carry(d.u);
-    fe_add(d.v, d.v, one);
-    fe_sq_o<kSO>(d.v3, d.v);
-    fe_mul_o<kSO>(d.v3, d.v3, d.v);
-    fe_sq_o<kSO>(x, d.v3);
-    fe_mul_o<kSO>(x, x, d.v);
-    fe_mul_o<kSO>(z, x, d.u);  // u v^7
-    d.uv7 = z;                 // (part 2 needs it again)
-  }
-  const uint32_t k = lane & 15;
-  const LaneTerms sq = c_lane_sq.t[lane], mu = c_lane_mul.t[lane];
-  const uint32_t zd = dist_from_lane0(z, lane);
-#endif
   uint32_t t0 = dist_sq(zd, sq, lane);
   uint32_t t1 = dist_sqn(t0, 2, sq, lane);
   t1 = dist_mul(zd, t1, mu, lane);
@@ -1300,7 +1099,8 @@ __device__ void r_decode_part1_lanes(RDecodeL& d, const uint32_t s[8], uint32_t 
   d.t0 = t0;
   d.t1 = t1;
 }
-// every lane of the wave calls; lane 0's x and result are r_decode_part2's
+// The rest: x of R with R's sign (false: no square root).  Same value as ge_frombytes.  Every lane
+// of the wave calls; x and the result are lane 0's.
 __device__ bool r_decode_part2_lanes(fe& x, RDecodeL& d, const uint32_t s[8], uint32_t lane) {
   const LaneTerms sq = c_lane_sq.t[lane], mu = c_lane_mul.t[lane];
   uint32_t t2 = dist_sqn(d.t2, 70, sq, lane);
@@ -1309,7 +1109,6 @@ __device__ bool r_decode_part2_lanes(fe& x, RDecodeL& d, const uint32_t s[8], ui
   uint32_t t0 = dist_mul(t1, d.t0, mu, lane);
   t0 = dist_sqn(t0, 2, sq, lane);
   fe vxx, chk;
-#if EDV_SMALL_DIST_EDGES
   // x = u v^3 (u v^7)^((p-5)/8), then v x^2, on the wave; lane 0 takes x, v x^2 and u
   uint32_t xd = dist_mul(dist_mul(dist_mul(t0, d.duv7, mu, lane), d.dv3, mu, lane), d.du, mu, lane);
   const uint32_t vxxd = dist_mul(dist_sq(xd, sq, lane), d.dv, mu, lane);
@@ -1322,44 +1121,20 @@ __device__ bool r_decode_part2_lanes(fe& x, RDecodeL& d, const uint32_t s[8], ui
   if (!fe_iszero(chk)) {
     fe_add(chk, vxx, u);
     if (!fe_iszero(chk)) return false;
-    fe_mul_o<kSO>(x, x, fe_const_sqrtm1());
+    fe_mul_chain(x, x, fe_const_sqrtm1());
   }
   if (fe_isnegative(x) != (s[7] >> 31)) {
     fe_neg(x, x);
     fe_carry(x);
   }
   return true;
-#else
-  fe pw;
-  dist_to_fe(pw, t0);  // (u v^7)^((p-5)/8), class C, in every lane
-  if (lane != 0) return false;
-  fe_mul_o<kSO>(x, pw, d.uv7);
-  fe_mul_o<kSO>(x, x, d.v3);
-  fe_mul_o<kSO>(x, x, d.u);   // u v^3 (u v^7)^((p-5)/8)
-  fe_sq_o<kSO>(vxx, x);
-  fe_mul_o<kSO>(vxx, vxx, d.v);
-  fe_sub(chk, vxx, d.u);
-  if (!fe_iszero(chk)) {
-    fe_add(chk, vxx, d.u);
-    if (!fe_iszero(chk)) return false;
-    fe_mul_o<kSO>(x, x, fe_const_sqrtm1());
-  }
-  if (fe_isnegative(x) != (s[7] >> 31)) {
-    fe_neg(x, x);
-    fe_carry(x);
-  }
-  return true;
-#endif
 }
 
 // verify_phase_hash for the single-request kernel: SHA-512(R || A || M) with the blocks' message
 // schedules on wave 0's lanes (lane j: block p0 + j of a pass of kHashPass blocks, its 80 words
 // into LDS) and only the rounds on lane 0 -- the schedule is ~35 % of a round's instructions, and
 // on one lane every instruction is on the critical path.  Every lane of the wave calls; lane 0's
-// h and result are verify_phase_hash's.  EDV_SMALL_HASH_LANES=0: verify_phase_hash on lane 0 (A/B).
-#ifndef EDV_SMALL_HASH_LANES
-#define EDV_SMALL_HASH_LANES 1
-#endif
+// h and result are verify_phase_hash's.
 constexpr int kHashPass = 8;
 constexpr int kHashRow = 81;  // u64 per block row (odd: the lanes' rows start in different banks)
 __device__ __forceinline__ void sha512_schedule_lds(uint64_t* out, uint64_t w[16]) {
@@ -1501,27 +1276,16 @@ __device__ __forceinline__ bool small_verify(SmallShared& sh, const uint32_t sig
   static_assert(RK <= 64 && RB <= 64, "one lane per row");
   constexpr int WK = RK <= 16 ? 16 : RK <= 32 ? 32 : 64, WB = RB <= 16 ? 16 : RB <= 32 ? 32 : 64;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#if EDV_SMALL_LANES
   RDecodeL rd;  // wave 2: R's decode, across the first barrier
-#else
-  RDecode rd;  // wave 2, lane 0: R's decode, across the first barrier
-#endif
   const bool in_range = key0 < key_count;
   const uint64_t key = in_range ? key0 : 0;
   if (wave == 0) EDV_SP(0);
   if (wave == 0) {
-#if EDV_SMALL_HASH_LANES
     uint32_t pk[8], h[8];
     load_words(pk, key_pk + 32 * key, 8);
     const bool hok = verify_phase_hash_lanes(h, sig, pk, msg, mlen, (uint32_t)lane, sh.sw);
     if (lane == 0) {
       const bool ok = hok && in_range && key_valid[key];
-#else
-    if (lane == 0) {
-      uint32_t pk[8], h[8];
-      load_words(pk, key_pk + 32 * key, 8);
-      const bool ok = verify_phase_hash(h, sig, pk, msg, mlen) && in_range && key_valid[key];
-#endif
 #pragma unroll
       for (int k = 0; k < 8; ++k) sh.h[k] = h[k];
       sh.ok_hash = ok ? 1 : 0;
@@ -1546,23 +1310,14 @@ __device__ __forceinline__ bool small_verify(SmallShared& sh, const uint32_t sig
     }
     EDV_SP(2);
   } else {
-#if EDV_SMALL_LANES
     r_decode_part1_lanes(rd, sig, (uint32_t)lane);
-#else
-    if (lane == 0) r_decode_part1(rd, sig);
-#endif
     EDV_SP(3);
   }
   __syncthreads();
   if (wave == 2) {
     fe x;
-#if EDV_SMALL_LANES
-    const bool dec = r_decode_part2_lanes(x, rd, sig, (uint32_t)lane);  // false: no root (lane 0)
-#endif
+    const bool dec = r_decode_part2_lanes(x, rd, sig, (uint32_t)lane);  // false: y^2 - 1 / (d y^2 + 1) has no root
     if (lane == 0) {
-#if !EDV_SMALL_LANES
-      const bool dec = r_decode_part2(x, rd, sig);  // false: y^2 - 1 / (d y^2 + 1) has no root
-#endif
       const bool zero_signed = (sig[7] >> 31) && fe_iszero(x);
       store_fe(sh.xr, x);
       sh.ok_r = (dec && is_canonical_point(sig) && !zero_signed) ? 1 : 0;
@@ -1597,14 +1352,14 @@ __device__ __forceinline__ bool small_verify(SmallShared& sh, const uint32_t sig
     load_fe(B.T, sh.base + 30);
     ge_cached c;
     ge_p1p1 t;
-    ge_p3_to_cached<kSO>(c, B);
-    ge_add<kSO>(t, P, c);
-    ge_p1p1_to_p2_addlike<kSO>(Q, t);  // R' = [h](-A) + [S]B, classes C
+    ge_p3_to_cached(c, B);
+    ge_add(t, P, c);
+    ge_p1p1_to_p2_addlike(Q, t);  // R' = [h](-A) + [S]B, classes C
     // Y' = y_R Z' needs only R's bytes (y_R as r_decode reads it): checked here, while wave 2 still
     // decodes, so one product follows the last barrier, not two
     fe yr, u, d;
     fe_frombytes(yr, sig);
-    fe_mul_o<kSO>(u, yr, Q.Z);
+    fe_mul_chain(u, yr, Q.Z);
     fe_sub(d, Q.Y, u);
     ok_y = fe_iszero(d);
   }
@@ -1612,7 +1367,7 @@ __device__ __forceinline__ bool small_verify(SmallShared& sh, const uint32_t sig
   if (wave != 0 || lane != 0) return false;
   fe xr, u, d;
   load_fe(xr, sh.xr);
-  fe_mul_o<kSO>(u, xr, Q.Z);
+  fe_mul_chain(u, xr, Q.Z);
   fe_sub(d, Q.X, u);  // X' - x_R Z'  (L)
   const bool ok = ok_y && sh.ok_hash && sh.ok_r && fe_iszero(d);
   EDV_SP(7);
@@ -1998,13 +1753,6 @@ struct edv_ctx {
   int key_sort = 2;
   uint64_t bls_pair_max = 32768;  // edv_options.bls_pair_lanes
   uint64_t bls_wave_max = 8192;   // edv_options.bls_wave_checks (8,192 checks 21.8 ms; the two-lane form 27.3)
-  // the small keyed path reads its packed inputs straight from pinned host memory (no H2D copy
-  // before the kernel); A/B switch EDV_SMALL_ZC=1
-  bool small_zero_copy = getenv("EDV_SMALL_ZC") != nullptr;
-  // phase events around a single request's small kernel (edv_stats.phase_ms): off unless
-  // EDV_SMALL_EVENTS=1 -- the two timestamps cost ~8 us of the round trip (119-126 against
-  // 128-134 us per engine call, profiles/r05y)
-  bool small_events = getenv("EDV_SMALL_EVENTS") != nullptr;
   // edv_verify_one's resident kernel (edv_resident_kernel): its mailbox, stream, request counter,
   // whether one was launched (it may have left since: box->running), the key window it serves, and
   // whether the path is on (EDV_RESIDENT=0: every single request launches edv_verify_small_kernel)
@@ -2514,13 +2262,14 @@ int launch_pipeline(edv_ctx* ctx, bool keyed, const void* d_sig, const void* d_k
 // verdict-byte pack; its duration lands in the comb phase of edv_stats.phase_ms.
 // host_ok8 (pinned host memory, n bytes): the kernel stores the verdict bytes there itself and
 // no pack kernel or D2H copy follows (d_words unused) -- two fewer GPU commands on the latency
-// path of one authenticate().
+// path of one authenticate(), and no phase events either: the two timestamps cost ~8 us of the
+// round trip (119-126 against 128-134 us per engine call, profiles/r05y).
 int launch_small(edv_ctx* ctx, const void* d_sig, const void* d_kidx, const void* d_msgs, const uint64_t* ms,
                  const uint64_t* me, uint64_t n, void* d_words, hipStream_t st, uint8_t* host_ok8 = nullptr) {
   if (n == 0) return 0;
   if (ctx->key_count == 0) return set_err(EDV_EINVAL, "no registered keys");
   hipEvent_t* ev = ctx->ev_sub[0];
-  const bool timed = ctx->small_events || !host_ok8;
+  const bool timed = !host_ok8;
   if (timed) HIP_TRY(hipEventRecord(ev[0], st));
   uint8_t* ok8 = host_ok8 ? host_ok8 : ctx->d_ok8;
   const uint32_t kc = (uint32_t)ctx->key_count;
@@ -2826,9 +2575,8 @@ static int host_submit(edv_ctx* ctx, bool keyed, const uint8_t* sig, uint64_t si
         if (mbytes) memcpy(hb + o_msg, msgs + m0, mbytes);
         stage_s += std::chrono::duration<double>(clk::now() - t0).count();
         hipStream_t st = ctx->stream;
-        const bool zc = keyed && !slots && ctx->small_zero_copy;  // the kernel reads hb over PCIe
-        char* db = zc ? hb : (char*)ctx->d_msg[sl].p;
-        if (!zc) HIP_TRY(hipMemcpyAsync(db, hb, c_bytes, hipMemcpyHostToDevice, st));
+        char* db = (char*)ctx->d_msg[sl].p;
+        HIP_TRY(hipMemcpyAsync(db, hb, c_bytes, hipMemcpyHostToDevice, st));
         ctx->last_h2d_bytes += c_bytes;
         void* d_sig_use = db;
         if (slots) {

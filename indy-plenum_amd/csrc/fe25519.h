@@ -182,35 +182,19 @@ EDV_HD void mad_acc5(uint64_t& acc, const uint32_t a[5], const uint32_t b[5]) {
 #endif
 
 // h = f * g.  f in W, g in L; h in C.  100 multiply-adds.
-// EDV_FE_MUL_ORDER 1 emits the products operand-major (for each f_i, one
-// product into each of the 10 accumulators), so consecutive v_mad_u64_u32 go
-// to different accumulators; 0 emits them accumulator-major.
-// EDV_FE_MUL_ORDER 2 computes the accumulators in order with the previous
-// limb's carry as the chain's initial addend (no separate 64-bit carry adds;
-// one accumulator live; a serial chain per multiply).
-#ifndef EDV_FE_MUL_ORDER
-#define EDV_FE_MUL_ORDER 2  // 2: -3% comb time vs 0 and 1 (tools/ab_keyed.py)
-#endif
-// EDV ORDER 3 (latency: one wave, one request): as 2, but limbs 0-4 and 5-9 run as two
-// independent carry-started chains (limb 5's starts from 0), so a lone wave can overlap them;
-// then the first chain's carry ripples through limbs 5-9 (32-bit steps) and the wrap adds
-// 19 x (both chains' final carries) to limb 0.  Output class C, as ORDER 2.
-EDV_HD void fe_join_halves(uint32_t o[10], uint64_t ca, uint64_t cb) {
-  uint64_t t = (uint64_t)o[5] + ca;
-  o[5] = (uint32_t)t & M25;
-  uint32_t c = (uint32_t)(t >> 25);  // < 2^14
-#pragma unroll
-  for (int k = 6; k < 10; ++k) {
-    const uint32_t u = o[k] + c;
-    o[k] = u & fe_mask(k);
-    c = u >> fe_width(k);
-  }
-  t = (uint64_t)o[0] + (cb + c) * 19u;  // carry out of limb 9 wraps as 19 * 2^0
-  o[0] = (uint32_t)t & M26;
-  o[1] += (uint32_t)(t >> 26);
-}
-template <int ORDER>
-EDV_HD void fe_mul_o(fe& h, const fe& f, const fe& g) {
+// The accumulators are computed in order with the previous limb's carry as the
+// chain's initial addend (no separate 64-bit carry adds; one accumulator live;
+// a serial chain per multiply).
+//
+// fe_mul / fe_sq forward to fe_mul_chain / fe_sq_chain, and the callers that
+// once named a product order (fe_sqn, fe_invert, ge_add, the addlike
+// conversions, comb_set_entry, the encode, the single-request kernel) call the
+// chain directly.  Both depths are the same code; the split is kept only
+// because the order in which the compiler inlines, and with it every kernel's
+// register allocation, follows the call depth, and the removal of the other
+// product orders left the device code byte-identical.  A change that
+// re-measures the kernels can fold the two names into one.
+EDV_HD void fe_mul_chain(fe& h, const fe& f, const fe& g) {
   EDV_ASSERT(EDV_IS_W(f) && EDV_IS_L(g));
   uint32_t g19[10], f2[10];
 #pragma unroll
@@ -218,88 +202,47 @@ EDV_HD void fe_mul_o(fe& h, const fe& f, const fe& g) {
     g19[k] = 19u * g.v[k];
     f2[k] = (k & 1) ? 2u * f.v[k] : f.v[k];
   }
-  if constexpr (ORDER == 2 || ORDER == 3) {
-    uint64_t c = 0, ca = 0;
-    uint32_t o[10];  // h may alias f or g
+  uint64_t c = 0;
+  uint32_t o[10];  // h may alias f or g
 #pragma unroll
-    for (int k = 0; k < 10; ++k) {
-      if (ORDER == 3 && k == 5) {
-        ca = c;
-        c = 0;
-      }
+  for (int k = 0; k < 10; ++k) {
 #if EDV_MAD_CHAIN
-      // the chain starts from the carry of limb k - 1 (one v_mad_u64_u32 per
-      // product, no separate 64-bit add of the carry, which the compiler's
-      // reassociation otherwise emits)
-      uint64_t a = c;
-      uint32_t fa[10], gb[10];
+    // the chain starts from the carry of limb k - 1 (one v_mad_u64_u32 per
+    // product, no separate 64-bit add of the carry, which the compiler's
+    // reassociation otherwise emits)
+    uint64_t a = c;
+    uint32_t fa[10], gb[10];
 #pragma unroll
-      for (int i = 0; i < 10; ++i) {
-        const int j = k - i;
-        fa[i] = ((i & 1) && (j & 1)) ? f2[i] : f.v[i];
-        gb[i] = j >= 0 ? g.v[j] : g19[j + 10];
-      }
-      mad_acc10(a, fa, gb);
+    for (int i = 0; i < 10; ++i) {
+      const int j = k - i;
+      fa[i] = ((i & 1) && (j & 1)) ? f2[i] : f.v[i];
+      gb[i] = j >= 0 ? g.v[j] : g19[j + 10];
+    }
+    mad_acc10(a, fa, gb);
 #else
-      uint64_t a = c;
+    uint64_t a = c;
 #pragma unroll
-      for (int i = 0; i < 10; ++i) {
-        const int j = k - i;
-        const uint32_t fi = ((i & 1) && (j & 1)) ? f2[i] : f.v[i];
-        const uint32_t gj = j >= 0 ? g.v[j] : g19[j + 10];
-        a += (uint64_t)fi * gj;
-      }
+    for (int i = 0; i < 10; ++i) {
+      const int j = k - i;
+      const uint32_t fi = ((i & 1) && (j & 1)) ? f2[i] : f.v[i];
+      const uint32_t gj = j >= 0 ? g.v[j] : g19[j + 10];
+      a += (uint64_t)fi * gj;
+    }
 #endif
-      o[k] = (uint32_t)a & fe_mask(k);
-      c = a >> fe_width(k);
-    }
-    if constexpr (ORDER == 3) {
-      fe_join_halves(o, ca, c);
-    } else {
-      const uint64_t t = (uint64_t)o[0] + c * 19u;  // carry out of limb 9 wraps as 19 * 2^0
-      o[0] = (uint32_t)t & M26;
-      o[1] += (uint32_t)(t >> 26);
-    }
-#pragma unroll
-    for (int k = 0; k < 10; ++k) h.v[k] = o[k];
-  } else {
-    uint64_t acc[10];
-    if constexpr (ORDER == 1) {
-#pragma unroll
-      for (int k = 0; k < 10; ++k) acc[k] = 0;
-#pragma unroll
-      for (int i = 0; i < 10; ++i) {
-#pragma unroll
-        for (int k = 0; k < 10; ++k) {
-          const int j = k - i;
-          const uint32_t fi = ((i & 1) && (j & 1)) ? f2[i] : f.v[i];
-          const uint32_t gj = j >= 0 ? g.v[j] : g19[j + 10];
-          acc[k] += (uint64_t)fi * gj;
-        }
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 10; ++k) {
-        uint64_t a = 0;
-#pragma unroll
-        for (int i = 0; i < 10; ++i) {
-          const int j = k - i;
-          const uint32_t fi = ((i & 1) && (j & 1)) ? f2[i] : f.v[i];
-          const uint32_t gj = j >= 0 ? g.v[j] : g19[j + 10];
-          a += (uint64_t)fi * gj;
-        }
-        acc[k] = a;
-      }
-    }
-    fe_carry64(h, acc);
+    o[k] = (uint32_t)a & fe_mask(k);
+    c = a >> fe_width(k);
   }
+  const uint64_t t = (uint64_t)o[0] + c * 19u;  // carry out of limb 9 wraps as 19 * 2^0
+  o[0] = (uint32_t)t & M26;
+  o[1] += (uint32_t)(t >> 26);
+#pragma unroll
+  for (int k = 0; k < 10; ++k) h.v[k] = o[k];
 }
-EDV_HD void fe_mul(fe& h, const fe& f, const fe& g) { fe_mul_o<EDV_FE_MUL_ORDER>(h, f, g); }
+EDV_HD void fe_mul(fe& h, const fe& f, const fe& g) { fe_mul_chain(h, f, g); }
 
-// h = f^2.  f in L; h in C.  55 multiply-adds.  With EDV_FE_MUL_ORDER 2 the
-// carry of limb k-1 is the initial addend of limb k's chain (as fe_mul).
-template <int ORDER>
-EDV_HD void fe_sq_o(fe& h, const fe& f) {
+// h = f^2.  f in L; h in C.  55 multiply-adds.  The carry of limb k-1 is the
+// initial addend of limb k's chain (as fe_mul).
+EDV_HD void fe_sq_chain(fe& h, const fe& f) {
   EDV_ASSERT(EDV_IS_L(f));
   uint32_t d[10], d2[10], d19[10], d38[10];
 #pragma unroll
@@ -309,17 +252,11 @@ EDV_HD void fe_sq_o(fe& h, const fe& f) {
     d19[k] = 19u * f.v[k];
     d38[k] = 38u * f.v[k];
   }
-  constexpr bool kChain = ORDER == 2 || ORDER == 3;
-  uint64_t acc[10];
-  uint64_t c = 0, ca = 0;
+  uint64_t c = 0;
   uint32_t o[10];
 #pragma unroll
   for (int k = 0; k < 10; ++k) {
-    if (ORDER == 3 && k == 5) {
-      ca = c;
-      c = 0;
-    }
-    uint64_t a = kChain ? c : 0;
+    uint64_t a = c;
     uint32_t pa[6], pb[6];
     int np = 0;
 #pragma unroll
@@ -331,7 +268,7 @@ EDV_HD void fe_sq_o(fe& h, const fe& f) {
         const bool wrap = i + j >= 10;
         const uint32_t fi = (i != j) ? d2[i] : d[i];
         const uint32_t fj = wrap ? (both_odd ? d38[j] : d19[j]) : (both_odd ? d2[j] : d[j]);
-        if (kChain && EDV_MAD_CHAIN) {
+        if (EDV_MAD_CHAIN) {
           pa[np] = fi;  // carry-started chain, one asm block per limb
           pb[np] = fj;
           ++np;
@@ -340,40 +277,28 @@ EDV_HD void fe_sq_o(fe& h, const fe& f) {
         }
       }
     }
-    if (kChain && EDV_MAD_CHAIN) {
+    if (EDV_MAD_CHAIN) {
       if (k & 1)
         mad_acc5(a, pa, pb);
       else
         mad_acc6(a, pa, pb);
     }
-    acc[k] = a;
-    if (kChain) {
-      o[k] = (uint32_t)a & fe_mask(k);
-      c = a >> fe_width(k);
-    }
+    o[k] = (uint32_t)a & fe_mask(k);
+    c = a >> fe_width(k);
   }
-  if (kChain) {
-    if (ORDER == 3) {
-      fe_join_halves(o, ca, c);
-    } else {
-      const uint64_t t = (uint64_t)o[0] + c * 19u;
-      o[0] = (uint32_t)t & M26;
-      o[1] += (uint32_t)(t >> 26);
-    }
+  const uint64_t t = (uint64_t)o[0] + c * 19u;
+  o[0] = (uint32_t)t & M26;
+  o[1] += (uint32_t)(t >> 26);
 #pragma unroll
-    for (int k = 0; k < 10; ++k) h.v[k] = o[k];
-  } else {
-    fe_carry64(h, acc);
-  }
+  for (int k = 0; k < 10; ++k) h.v[k] = o[k];
 }
-EDV_HD void fe_sq(fe& h, const fe& f) { fe_sq_o<EDV_FE_MUL_ORDER>(h, f); }
+EDV_HD void fe_sq(fe& h, const fe& f) { fe_sq_chain(h, f); }
 
 // h = f^(2^n), n >= 1.
-template <int ORDER = EDV_FE_MUL_ORDER>
 EDV_HDNI void fe_sqn(fe& h, const fe& f, int n) {
-  fe_sq_o<ORDER>(h, f);
+  fe_sq_chain(h, f);
 #pragma unroll 1
-  for (int i = 1; i < n; ++i) fe_sq_o<ORDER>(h, h);
+  for (int i = 1; i < n; ++i) fe_sq_chain(h, h);
 }
 
 // One 32-bit carry pass: any class up to 2^31 per limb -> C.
@@ -456,33 +381,30 @@ EDV_HD uint32_t fe_isnegative(const fe& f) {
 }
 
 // z^(2^255 - 21) = z^-1 (ref10 addition chain: 254 squarings, 11 multiplies).
-// ORDER as fe_mul_o: 1 gives ten independent accumulator chains per product
-// (for latency-bound callers at low occupancy, e.g. the batched encode).
-template <int ORDER = EDV_FE_MUL_ORDER>
 EDV_HDNI void fe_invert(fe& out, const fe& z) {
   fe t0, t1, t2, t3;
-  fe_sq_o<ORDER>(t0, z);
-  fe_sqn<ORDER>(t1, t0, 2);
-  fe_mul_o<ORDER>(t1, z, t1);
-  fe_mul_o<ORDER>(t0, t0, t1);
-  fe_sq_o<ORDER>(t2, t0);
-  fe_mul_o<ORDER>(t1, t1, t2);
-  fe_sqn<ORDER>(t2, t1, 5);
-  fe_mul_o<ORDER>(t1, t2, t1);
-  fe_sqn<ORDER>(t2, t1, 10);
-  fe_mul_o<ORDER>(t2, t2, t1);
-  fe_sqn<ORDER>(t3, t2, 20);
-  fe_mul_o<ORDER>(t2, t3, t2);
-  fe_sqn<ORDER>(t2, t2, 10);
-  fe_mul_o<ORDER>(t1, t2, t1);
-  fe_sqn<ORDER>(t2, t1, 50);
-  fe_mul_o<ORDER>(t2, t2, t1);
-  fe_sqn<ORDER>(t3, t2, 100);
-  fe_mul_o<ORDER>(t2, t3, t2);
-  fe_sqn<ORDER>(t2, t2, 50);
-  fe_mul_o<ORDER>(t1, t2, t1);
-  fe_sqn<ORDER>(t1, t1, 5);
-  fe_mul_o<ORDER>(out, t1, t0);
+  fe_sq_chain(t0, z);
+  fe_sqn(t1, t0, 2);
+  fe_mul_chain(t1, z, t1);
+  fe_mul_chain(t0, t0, t1);
+  fe_sq_chain(t2, t0);
+  fe_mul_chain(t1, t1, t2);
+  fe_sqn(t2, t1, 5);
+  fe_mul_chain(t1, t2, t1);
+  fe_sqn(t2, t1, 10);
+  fe_mul_chain(t2, t2, t1);
+  fe_sqn(t3, t2, 20);
+  fe_mul_chain(t2, t3, t2);
+  fe_sqn(t2, t2, 10);
+  fe_mul_chain(t1, t2, t1);
+  fe_sqn(t2, t1, 50);
+  fe_mul_chain(t2, t2, t1);
+  fe_sqn(t3, t2, 100);
+  fe_mul_chain(t2, t3, t2);
+  fe_sqn(t2, t2, 50);
+  fe_mul_chain(t1, t2, t1);
+  fe_sqn(t1, t1, 5);
+  fe_mul_chain(out, t1, t0);
 }
 
 // z^(2^252 - 3) (for square roots; 250 squarings, 11 multiplies).

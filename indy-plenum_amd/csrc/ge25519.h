@@ -68,14 +68,11 @@ EDV_HD void ge_p3_to_p2(ge_p2& r, const ge_p3& p) {
   r.Z = p.Z;
 }
 // p3 (all C) -> cached (YplusX L, YminusX L, Z C, T2d C).
-// ORDER picks fe_mul_o's product order (fe25519.h): the default for throughput, 1 (ten
-// independent accumulators) where one lane's latency is what counts (the small-batch kernel).
-template <int ORDER = EDV_FE_MUL_ORDER>
 EDV_HD void ge_p3_to_cached(ge_cached& r, const ge_p3& p) {
   fe_add(r.YplusX, p.Y, p.X);
   fe_sub(r.YminusX, p.Y, p.X);
   r.Z = p.Z;
-  fe_mul_o<ORDER>(r.T2d, p.T, fe_const_d2());
+  fe_mul_chain(r.T2d, p.T, fe_const_d2());
 }
 
 // r = 2p.  p in C.  Output: X W, Y L, Z L, T C.
@@ -102,15 +99,14 @@ EDV_HD void ge_p3_dbl(ge_p1p1& r, const ge_p3& p) {
 }
 
 // r = p + q.  p in C, q cached.  Output: X L, Y L, Z L, T W.
-template <int ORDER = EDV_FE_MUL_ORDER>
 EDV_HD void ge_add(ge_p1p1& r, const ge_p3& p, const ge_cached& q) {
   fe s, a, b, c, d;
   fe_add(s, p.Y, p.X);
-  fe_mul_o<ORDER>(a, s, q.YplusX);
+  fe_mul_chain(a, s, q.YplusX);
   fe_sub(s, p.Y, p.X);
-  fe_mul_o<ORDER>(b, s, q.YminusX);
-  fe_mul_o<ORDER>(c, p.T, q.T2d);
-  fe_mul_o<ORDER>(d, p.Z, q.Z);
+  fe_mul_chain(b, s, q.YminusX);
+  fe_mul_chain(c, p.T, q.T2d);
+  fe_mul_chain(d, p.Z, q.Z);
   fe_add(d, d, d);            // L
   fe_sub(r.X, a, b);          // L
   fe_add(r.Y, a, b);          // L
@@ -161,41 +157,12 @@ EDV_HD void ge_msub(ge_p1p1& r, const ge_p3& p, const ge_niels& q) {
   fe_add(r.T, d, c);
 }
 
-// r = p + q or p - q (neg) for affine q, straight to p3: ge_madd/ge_msub +
+// r = p + q or p - q (neg) for cached q, straight to p3: ge_add/ge_sub +
 // ge_p1p1_to_p3_*, with the sign folded into selects on p's side so the
-// table entry is used exactly as loaded.  -q = (y-x, y+x, -2dxy), so for neg
+// cached point is used exactly as loaded.  -q = (Y-X, Y+X, Z, -T2d), so for neg
 // the Y+X / Y-X multiplicands swap (a, b come out swapped: X3 = b - a) and
-// 2Z +/- T*2dxy swap roles (Z3 = 2Z - c, T3 = 2Z + c).  Classes: a, b, c C;
+// 2ZZ' +/- T*T2d swap roles (Z3 = d - c, T3 = d + c).  Classes: a, b, c C;
 // X3, Y3, plus L; minus W.
-EDV_HD void ge_madd_signed(ge_p3& r, const ge_p3& p, const ge_niels& q, bool neg) {
-  fe sp, sm, a, b, c, d, plus, minus, t;
-  fe_add(sp, p.Y, p.X);       // L
-  fe_sub(sm, p.Y, p.X);       // L
-  t = sp;
-  fe_cmov(sp, sm, neg);
-  fe_cmov(sm, t, neg);
-  fe_mul(a, sp, q.ypx);
-  fe_mul(b, sm, q.ymx);
-  fe_mul(c, p.T, q.xy2d);
-  fe_add(d, p.Z, p.Z);        // L
-  fe X3, Y3;
-  fe_sub(X3, a, b);           // L
-  fe_sub(t, b, a);            // L
-  fe_cmov(X3, t, neg);
-  fe_add(Y3, a, b);           // L
-  fe_add(plus, d, c);         // L
-  fe_sub(minus, d, c);        // W
-  fe zs = plus, ts = minus;   // r.Z-side / r.T-side of the p1p1 point
-  fe_cmov(zs, minus, neg);    // W
-  fe_cmov(ts, plus, neg);     // W
-  fe_mul(r.X, ts, X3);
-  fe_mul(r.Y, zs, Y3);
-  fe_mul(r.Z, minus, plus);
-  fe_mul(r.T, X3, Y3);
-}
-
-// r = p + q or p - q (neg) for cached q, straight to p3 (ge_add/ge_sub +
-// ge_p1p1_to_p3_*), the sign folded in as in ge_madd_signed.
 EDV_HD void ge_add_signed(ge_p3& r, const ge_p3& p, const ge_cached& q, bool neg) {
   fe sp, sm, a, b, c, d, plus, minus, t;
   fe_add(sp, p.Y, p.X);
@@ -228,12 +195,11 @@ EDV_HD void ge_add_signed(ge_p3& r, const ge_p3& p, const ge_cached& q, bool neg
 // in W, ge_sub/msub leave Z in W; ge_p2_dbl leaves X in W and T carried.
 // T3 = Y * X (not X * Y): the four products then need 2 * Y / 2 * T odd limbs
 // and 19 * X / 19 * Z premultiplies only (fe_mul's f2 / g19), not three each.
-template <int ORDER = EDV_FE_MUL_ORDER>
 EDV_HD void ge_p1p1_to_p3_addlike(ge_p3& r, const ge_p1p1& p) {  // T is W
-  fe_mul_o<ORDER>(r.X, p.T, p.X);
-  fe_mul_o<ORDER>(r.Y, p.Y, p.Z);
-  fe_mul_o<ORDER>(r.Z, p.T, p.Z);
-  fe_mul_o<ORDER>(r.T, p.Y, p.X);
+  fe_mul_chain(r.X, p.T, p.X);
+  fe_mul_chain(r.Y, p.Y, p.Z);
+  fe_mul_chain(r.Z, p.T, p.Z);
+  fe_mul_chain(r.T, p.Y, p.X);
 }
 EDV_HD void ge_p1p1_to_p3_sublike(ge_p3& r, const ge_p1p1& p) {  // Z is W
   fe_mul(r.X, p.X, p.T);
@@ -241,11 +207,10 @@ EDV_HD void ge_p1p1_to_p3_sublike(ge_p3& r, const ge_p1p1& p) {  // Z is W
   fe_mul(r.Z, p.Z, p.T);
   fe_mul(r.T, p.X, p.Y);
 }
-template <int ORDER = EDV_FE_MUL_ORDER>
 EDV_HD void ge_p1p1_to_p2_addlike(ge_p2& r, const ge_p1p1& p) {
-  fe_mul_o<ORDER>(r.X, p.T, p.X);
-  fe_mul_o<ORDER>(r.Y, p.Y, p.Z);
-  fe_mul_o<ORDER>(r.Z, p.T, p.Z);
+  fe_mul_chain(r.X, p.T, p.X);
+  fe_mul_chain(r.Y, p.Y, p.Z);
+  fe_mul_chain(r.Z, p.T, p.Z);
 }
 EDV_HD void ge_p1p1_to_p2_sublike(ge_p2& r, const ge_p1p1& p) {
   fe_mul(r.X, p.X, p.T);

@@ -36,7 +36,6 @@ struct HostComb {
     memcpy(n.ymx.v, p + 10, 40);
     memcpy(n.xy2d.v, p + 20, 40);
   }
-  uint32_t touch(int, int) const { return 0; }
 };
 
 std::vector<uint32_t> g_btab;  // W = 8 comb of B, built by the device code on first use
@@ -151,22 +150,9 @@ int edv_host_sc_is_canonical(const uint8_t s[32]) {
 
 // out = canonical bytes of (a * b) for field elements given as 32-byte LE
 // integers < 2^255 (exercises fe_frombytes, fe_mul, fe_sq, fe_tobytes).
-// mode: bit 0 square; bits 1-2 the product order (0: the default, else fe_mul_o / fe_sq_o<order>)
+// mode: bit 0 square
 static void fe_mul_mode(fe& fo, const fe& fa, const fe& fb, int mode) {
-  const bool sq = mode & 1;
-  switch (mode >> 1) {
-    case 1:
-      sq ? fe_sq_o<1>(fo, fa) : fe_mul_o<1>(fo, fa, fb);
-      break;
-    case 2:
-      sq ? fe_sq_o<2>(fo, fa) : fe_mul_o<2>(fo, fa, fb);
-      break;
-    case 3:
-      sq ? fe_sq_o<3>(fo, fa) : fe_mul_o<3>(fo, fa, fb);
-      break;
-    default:
-      sq ? fe_sq(fo, fa) : fe_mul(fo, fa, fb);
-  }
+  (mode & 1) ? fe_sq(fo, fa) : fe_mul(fo, fa, fb);
   EDV_ASSERT(EDV_IS_C(fo));
 }
 void edv_host_fe_mul(uint8_t out[32], const uint8_t a[32], const uint8_t b[32], int mode) {

@@ -28,7 +28,6 @@
 #include <emmintrin.h>
 #include <sched.h>
 #include <unistd.h>
-#include <sys/syscall.h>
 
 #include <stdint.h>
 #include <stdio.h>
@@ -325,11 +324,6 @@ inline const DkEntry* dk_entries(PyObject* o, Py_ssize_t& n) {
 }
 #define EDV_HAVE_DK 1
 #endif
-bool g_scan_direct = true;  // EDV_SCAN_DIRECT=0: PyDict_Next instead (A/B); set per scan call
-inline bool g_scan_direct_env() {
-  const char* e = getenv("EDV_SCAN_DIRECT");
-  return !(e && e[0] == '0');
-}
 
 bool w_str_eq(PyObject* a, PyObject* b) {  // canonical kinds: equal strings have equal kinds
   const Py_ssize_t n = PyUnicode_GET_LENGTH(a);
@@ -397,7 +391,7 @@ WRes wser_dict(PyObject* d, int level, PyObject* ignore, OutBuf& out, PyObject* 
   };
 #ifdef EDV_HAVE_DK
   Py_ssize_t ne = 0;
-  const DkEntry* ent = g_scan_direct ? dk_entries(d, ne) : nullptr;
+  const DkEntry* ent = dk_entries(d, ne);
   if (ent) {
     for (Py_ssize_t e = 0; e < ne; ++e)  // insertion order, deleted entries (value NULL) skipped
       if (ent[e].v && !take(ent[e].k, ent[e].v)) return kFail;
@@ -1189,7 +1183,6 @@ PyObject* py_kid_map_size(PyObject*, PyObject* cap) {
 // Writes into the engine's pinned memory that only the DMA reads back: non-temporal stores
 // (no read-for-ownership of the destination lines, nothing evicted from the worker's cache).
 // The caller fences (_mm_sfence) before publishing what it wrote to another thread.
-bool g_scan_nt = true;  // EDV_SCAN_NT=0: ordinary stores (A/B); set per scan call
 inline void nt_slot96(char* dst, const unsigned char* text, size_t n) {  // dst 16-byte aligned, n <= 95
   alignas(16) char b[96];
   memcpy(b, text, n);
@@ -1251,10 +1244,8 @@ int cpu_budget() {
 constexpr int kMaxScanThreads = 48;
 int scan_threads(Py_ssize_t n, int want) {
   if (want > 0) return std::min(want, 64);
-  const char* env = getenv("EDV_SCAN_THREADS");  // at most this many workers (A/B)
-  const int env_max = env ? atoi(env) : 0;
   const Py_ssize_t by_size = n / 2048 + 1;
-  const Py_ssize_t cap = env_max > 0 ? (Py_ssize_t)env_max : (Py_ssize_t)kMaxScanThreads;
+  const Py_ssize_t cap = kMaxScanThreads;
   return (int)std::max<Py_ssize_t>(1, std::min<Py_ssize_t>({(Py_ssize_t)cpu_budget(), cap, by_size}));
 }
 
@@ -1271,7 +1262,7 @@ int scan_threads(Py_ssize_t n, int want) {
 // f(worker, begin, end) per chunk.
 constexpr Py_ssize_t kScanChunk = 1024;
 
-// Software prefetch of the requests ahead of the worker (on unless EDV_SCAN_PREFETCH=0): a request is
+// Software prefetch of the requests ahead of the worker: a request is
 // ~10 small objects scattered over the heap (each json-decoded on its own), so the scan waits on
 // one cache miss after another.  Stages, each reading only what an earlier stage fetched: the
 // dict of item i + 10; its key table (i + 7); its keys and values (i + 4); the key tables of
@@ -1281,29 +1272,27 @@ inline void pf(const void* p) { __builtin_prefetch(p); }
 inline void pf_lines(const void* p, int n) {
   for (int k = 0; k < n; ++k) __builtin_prefetch((const char*)p + 64 * k);
 }
-// (K scales every distance: EDV_SCAN_PF=2 or 3 prefetches two or three times as far ahead, A/B)
-template <int K = 1>
 inline void prefetch_ahead(PyObject** items, Py_ssize_t i, Py_ssize_t b) {
-  if (i + 10 * K < b) pf(items[i + 10 * K]);
-  if (i + 7 * K < b) {
-    PyObject* o = items[i + 7 * K];
+  if (i + 10 < b) pf(items[i + 10]);
+  if (i + 7 < b) {
+    PyObject* o = items[i + 7];
     if (Py_TYPE(o) == &PyDict_Type) pf_lines(((PyDictObject*)o)->ma_keys, 3);
   }
 #ifdef EDV_HAVE_DK
   Py_ssize_t n;
-  if (i + 4 * K < b)
-    if (const DkEntry* e = dk_entries(items[i + 4 * K], n))
+  if (i + 4 < b)
+    if (const DkEntry* e = dk_entries(items[i + 4], n))
       for (Py_ssize_t j = 0; j < n; ++j)
         if (e[j].v) {
           pf(e[j].k);
           pf_lines(e[j].v, 2);
         }
-  if (i + 2 * K < b)
-    if (const DkEntry* e = dk_entries(items[i + 2 * K], n))
+  if (i + 2 < b)
+    if (const DkEntry* e = dk_entries(items[i + 2], n))
       for (Py_ssize_t j = 0; j < n; ++j)
         if (e[j].v && Py_TYPE(e[j].v) == &PyDict_Type) pf_lines(((PyDictObject*)e[j].v)->ma_keys, 3);
-  if (i + K < b)
-    if (const DkEntry* e = dk_entries(items[i + K], n))
+  if (i + 1 < b)
+    if (const DkEntry* e = dk_entries(items[i + 1], n))
       for (Py_ssize_t j = 0; j < n; ++j) {
         Py_ssize_t n2;
         if (e[j].v)
@@ -1337,55 +1326,6 @@ void run_chunks(Py_ssize_t n, int t, F&& f, Py_ssize_t chunk = kScanChunk) {
     }
   };
   HostPool::get().run(t, body);
-}
-
-// EDV_SCAN_NUMA=1 (A/B): the scan's helper threads run on the CPUs of the NUMA node that holds
-// the batch's request objects (the node of the pages of three sampled dicts, get_mempolicy), so a
-// batch built on another node than the helpers happened to run on is not walked across the
-// socket link.  The calling thread is left where it is.  Measured slower on the GPU box (2 x EPYC
-// 9575F, NPS1, a 16-CPU quota over 256 CPUs): 39.0-48.5 against 49.1-50.6 M/s whole node
-// (profiles/r10y) -- off by default.
-inline int numa_node_cpus(int node, cpu_set_t& set) {
-  char path[96];
-  snprintf(path, sizeof path, "/sys/devices/system/node/node%d/cpulist", node);
-  FILE* f = fopen(path, "r");
-  if (!f) return -1;
-  char buf[4096];
-  const size_t len = fread(buf, 1, sizeof buf - 1, f);
-  fclose(f);
-  buf[len] = 0;
-  CPU_ZERO(&set);
-  int count = 0;
-  for (char* p = buf; *p && *p != '\n';) {
-    char* end;
-    long a = strtol(p, &end, 10), b = a;
-    if (end == p) break;
-    if (*end == '-') b = strtol(end + 1, &end, 10);
-    for (long c = a; c <= b && c < CPU_SETSIZE; ++c, ++count) CPU_SET((int)c, &set);
-    p = *end == ',' ? end + 1 : end;
-  }
-  return count;
-}
-inline void numa_follow(PyObject** items, Py_ssize_t n) {
-  static const bool on = getenv("EDV_SCAN_NUMA") && getenv("EDV_SCAN_NUMA")[0] == '1';
-  if (!on) return;
-  int votes[4] = {-1, -1, -1, -1};
-  const Py_ssize_t at[3] = {0, n / 2, n - 1};
-  for (int k = 0; k < 3; ++k) {
-    int node = -1;
-    // MPOL_F_NODE | MPOL_F_ADDR: the node of the page holding the address
-    if (syscall(SYS_get_mempolicy, &node, nullptr, 0UL, (void*)items[at[k]], 3UL) == 0) votes[k] = node;
-  }
-  const int node = votes[0] >= 0 && (votes[0] == votes[1] || votes[0] == votes[2]) ? votes[0]
-                   : votes[1] >= 0 && votes[1] == votes[2]                      ? votes[1]
-                                                                                  : votes[0];
-  if (node < 0) return;
-  cpu_set_t set, mine;
-  if (numa_node_cpus(node, set) <= 0 || sched_getaffinity(0, sizeof mine, &mine) != 0) return;
-  CPU_AND(&set, &set, &mine);
-  if (CPU_COUNT(&set) == 0) return;
-  HostPool& pool = HostPool::get();
-  if (!pool.same_affinity(set)) pool.set_affinity(set);
 }
 
 // Scratch kept across calls.  A fresh 1M-request batch would otherwise touch
@@ -1707,7 +1647,6 @@ PyObject* scan_impl_body(PyObject* args, bool unique_form, PyRefs& refs) {
   // Python path), base58 decode, serialization, and the identifier's slot in
   // the worker's own table of distinct identifiers
   const int t = scan_threads(n, want_threads);
-  if (t > 1 && n > 0) numa_follow(items, n);
   std::vector<ScanBuf>& bufs = S.bufs;  // bufs[t]: items redone under the GIL
   if (bufs.size() < (size_t)t + 1) bufs.resize((size_t)t + 1);
   for (ScanBuf& b : bufs) {
@@ -1730,7 +1669,7 @@ PyObject* scan_impl_body(PyObject* args, bool unique_form, PyRefs& refs) {
   std::vector<WorkerIdrs> tabs((size_t)t);
   // remembered dict shapes (shaped_dict); EDV_SCAN_SHAPES=0: wser_dict for every request (A/B)
   const char* shape_env = getenv("EDV_SCAN_SHAPES");
-  const bool shapes = g_scan_direct_env() && !(shape_env && shape_env[0] == '0');
+  const bool shapes = !(shape_env && shape_env[0] == '0');
   for (WorkerIdrs& w : tabs) {
     w.slot.reset(1024);
 #ifdef EDV_HAVE_DK
@@ -1798,7 +1737,7 @@ PyObject* scan_impl_body(PyObject* args, bool unique_form, PyRefs& refs) {
     const uint64_t pos = got & ((1ull << kSeqShift) - 1);
     if (copier.chunk_seq) copier.chunk_seq[(size_t)(a / kStageChunk)].store((uint32_t)seq, std::memory_order_relaxed);
     if (pos + total > smsg_cap) {
-      if (g_scan_nt) _mm_sfence();
+      _mm_sfence();
       staged_ok = false;  // the buffer was sized from earlier batches: the caller re-scans unstaged
       copier.res_end[seq].store(pos + 1, std::memory_order_release);  // (nothing of it is copied)
       copier.slot_done[(size_t)(a / kStageChunk)].store(1, std::memory_order_release);
@@ -1812,10 +1751,7 @@ PyObject* scan_impl_body(PyObject* args, bool unique_form, PyRefs& refs) {
       char* ds = dsig + (size_t)i * sig_slot;
       st0[i] = en0[i] = at;
       if (x.state == 1 && x.text) {  // the slot was written in the item loop
-        if (g_scan_nt)
-          nt_copy(smsg + at, sb.ser.data() + x.ser_at, x.ser_len);
-        else
-          memcpy(smsg + at, sb.ser.data() + x.ser_at, x.ser_len);
+        nt_copy(smsg + at, sb.ser.data() + x.ser_at, x.ser_len);
         at += x.ser_len;
         en0[i] = at;
         continue;
@@ -1841,7 +1777,7 @@ PyObject* scan_impl_body(PyObject* args, bool unique_form, PyRefs& refs) {
       at += ls + lm - 64;
       en0[i] = at;
     }
-    if (g_scan_nt) _mm_sfence();  // the chunk's non-temporal stores before the copier sees the chunk
+    _mm_sfence();  // the chunk's non-temporal stores before the copier sees the chunk
     copier.res_end[seq].store(pos + total + 1, std::memory_order_release);
     copier.slot_done[(size_t)(a / kStageChunk)].store(1, std::memory_order_release);
   };
@@ -1871,19 +1807,6 @@ PyObject* scan_impl_body(PyObject* args, bool unique_form, PyRefs& refs) {
     }
     copier.start();
   }
-  // software prefetch ahead of the workers (prefetch_ahead): the scan 18.4-19.8 vs 19.7-21.7 ms per
-  // 1M on the box's 16 CPUs, alternating in one process (profiles/r05p/scan_ab.log); EDV_SCAN_PREFETCH=0
-  // turns it off
-  const char* pf_env = getenv("EDV_SCAN_PREFETCH");
-  const bool prefetch = !(pf_env && pf_env[0] == '0');
-  const char* pfs_env = getenv("EDV_SCAN_PF");  // the distances' scale (A/B): 1 (default), 2, 3
-  const int pf_scale = pfs_env ? atoi(pfs_env) : 1;
-  const char* dir_env = getenv("EDV_SCAN_DIRECT");
-  g_scan_direct = !(dir_env && dir_env[0] == '0');
-  // non-temporal stores for what only the DMA reads: the staged scan's slots and messages
-  const char* nt_env = getenv("EDV_SCAN_NT");
-  g_scan_nt = staged && !(nt_env && nt_env[0] == '0');
-  const bool nt_slots = g_scan_nt;
   run_chunks(n, t, [&](int w, Py_ssize_t a, Py_ssize_t b) {
     ScanBuf& sb = bufs[(size_t)w];
     WorkerIdrs& tab = tabs[(size_t)w];
@@ -1894,14 +1817,9 @@ PyObject* scan_impl_body(PyObject* args, bool unique_form, PyRefs& refs) {
       x = ScanItem{};
       idr_of[(size_t)i] = nullptr;
       if (kid_out) kid_out[i] = 0xffffffffu;
-      if (prefetch) {
-        if (pf_scale == 2)
-          prefetch_ahead<2>(items, i, b);
-        else if (pf_scale == 3)
-          prefetch_ahead<3>(items, i, b);
-        else
-          prefetch_ahead<1>(items, i, b);
-      }
+      // software prefetch ahead of the worker: the scan 18.4-19.8 vs 19.7-21.7 ms per 1M on the
+      // box's 16 CPUs, alternating in one process (profiles/r05p/scan_ab.log)
+      prefetch_ahead(items, i, b);
       if (!PyDict_CheckExact(m)) continue;
       // one pass over the request's keys: its signing serialization (kept if the item stays on
       // the fast path) and the signature and identifier values
@@ -1954,7 +1872,7 @@ PyObject* scan_impl_body(PyObject* args, bool unique_form, PyRefs& refs) {
         x.text = 1;
         x.sig_len = 64;
         char* ds = dsig + (size_t)i * sig_slot;  // slot: the text, zero padding, its length in the last byte
-        if (nt_slots && ((uintptr_t)ds & 15) == 0) {
+        if (staged && ((uintptr_t)ds & 15) == 0) {  // non-temporal: only the DMA reads the staged slots
           nt_slot96(ds, x.sp, (size_t)x.ns);
         } else {
           memcpy(ds, x.sp, (size_t)x.ns);
@@ -2711,7 +2629,6 @@ PyObject* py_keys_known(PyObject*, PyObject* args) {
   // cached.  Reads stay in bounds (slot < size, entry < nentries); a stale guess only wastes a
   // prefetch.
   constexpr Py_ssize_t kD = 8;
-  static const bool prefetch = !(getenv("EDV_KEYS_PREFETCH") && getenv("EDV_KEYS_PREFETCH")[0] == '0');  // A/B
   const auto slot_of = [](PyObject* d, Py_hash_t h, const DkEntry*& ent, Py_ssize_t& ne) -> Py_ssize_t {
     const DkHead* k = (const DkHead*)((const PyDictObject*)d)->ma_keys;
     ent = dk_entries(d, ne);
@@ -2748,21 +2665,21 @@ PyObject* py_keys_known(PyObject*, PyObject* args) {
     };
     const DkEntry* ent;
     Py_ssize_t ne, ix;
-    if (prefetch && j + 4 * kD < n) {  // link 1: the index slots
+    if (j + 4 * kD < n) {  // link 1: the index slots
       const Py_hash_t h = hash_of(PyList_GET_ITEM(idrs, j + 4 * kD));
       if (h != -1) {
         pf_slot(clients, h);
         pf_slot(fk, h);
       }
     }
-    if (prefetch && j + 3 * kD < n) {  // link 2: the entries
+    if (j + 3 * kD < n) {  // link 2: the entries
       const Py_hash_t h = hash_at(j + 3 * kD);
       if (h != -1) {
         if ((ix = slot_of(clients, h, ent, ne)) >= 0) __builtin_prefetch(&ent[ix]);
         if ((ix = slot_of(fk, h, ent, ne)) >= 0) __builtin_prefetch(&ent[ix]);
       }
     }
-    if (prefetch && j + 2 * kD < n) {  // link 3: the keys, the nym dicts and the (verkey, key) tuples
+    if (j + 2 * kD < n) {  // link 3: the keys, the nym dicts and the (verkey, key) tuples
       const Py_hash_t h = hash_at(j + 2 * kD);
       if (h != -1) {
         if ((ix = slot_of(clients, h, ent, ne)) >= 0 && ent[ix].h == h) {
@@ -2772,7 +2689,7 @@ PyObject* py_keys_known(PyObject*, PyObject* args) {
         if ((ix = slot_of(fk, h, ent, ne)) >= 0 && ent[ix].h == h) __builtin_prefetch(ent[ix].v);
       }
     }
-    if (prefetch && j + kD < n) {  // link 4: the nym dicts' key tables and the tuples' key bytes
+    if (j + kD < n) {  // link 4: the nym dicts' key tables and the tuples' key bytes
       const Py_hash_t h = hash_at(j + kD);
       if (h != -1) {
         if ((ix = slot_of(clients, h, ent, ne)) >= 0 && ent[ix].h == h && ent[ix].v &&
@@ -2960,7 +2877,6 @@ PyObject* py_keys_known_flat(PyObject* self, PyObject* args) {
     std::vector<PyObject*> got((size_t)n, nullptr);
     std::vector<uint8_t> undecided((size_t)n, 0);
     PyObject** items = ((PyListObject*)idrs)->ob_item;
-    static const bool prefetch = !(getenv("EDV_KEYS_PREFETCH") && getenv("EDV_KEYS_PREFETCH")[0] == '0');  // A/B
     run_chunks(n, scan_threads(n, 0), [&](int, Py_ssize_t a, Py_ssize_t b) {
       // each lookup is a chain of ~10 dependent cache misses (index slot, entry, key text, nym
       // dict, its table, tuple, key bytes): the identifiers 1-4 x kPD ahead walk the same chains
@@ -2968,7 +2884,7 @@ PyObject* py_keys_known_flat(PyObject* self, PyObject* args) {
       // prefetch), so the lookups below find their lines cached -- keys_known's pipeline, per worker
       constexpr Py_ssize_t kPD = 6;
       for (Py_ssize_t j = a; j < b; ++j) {
-        if (prefetch) keys_prefetch_links(clients, fk, items, j, b, kPD);
+        keys_prefetch_links(clients, fk, items, j, b, kPD);
         PyObject* idr = items[j];
         PyObject *nym = nullptr, *vk = nullptr, *e = nullptr, *key = nullptr;
         int r = w_dict_get_str(clients, idr, &nym);

@@ -136,8 +136,7 @@ EDV_HD bool verify_phase_table(const uint32_t pk[8], TA& ta) {
 #endif                  // (tools/gpu_basew.sh, tools/gpu_ab_b22.sh)
 constexpr int kBaseW = EDV_BASE_W;  // base-point comb window: 11 rows x 2^23 entries (11 GiB) at W = 24
 template <class TA, class CB>
-EDV_HD uint32_t verify_phase_dsm_point(ge_p3& Q, const uint32_t h[8], const uint32_t S[8], const TA& ta,
-                                       const CB& cb) {
+EDV_HD void verify_phase_dsm_point(ge_p3& Q, const uint32_t h[8], const uint32_t S[8], const TA& ta, const CB& cb) {
   // radix-16 digits of h, top first: shift the recoded words left 4 bits per
   // digit (static register indexing; see CombDigits)
   uint32_t hy[8];
@@ -167,7 +166,7 @@ EDV_HD uint32_t verify_phase_dsm_point(ge_p3& Q, const uint32_t h[8], const uint
     ta.load(m - 1, c);  // m = 0: the identity (an address select in the accessor)
     ge_add_signed(Q, Q, c, e < 0);
   }
-  return comb_mul_add<kBaseW>(Q, S, cb);  // the base comb's prefetch sink (comb.h)
+  comb_mul_add<kBaseW>(Q, S, cb);
 }
 
 // Split tables for keys shared by many requests (the general path's distinct
@@ -215,8 +214,8 @@ EDV_HD bool verify_phase_table_split(const uint32_t pk[8], const TAS& tas) {
 }
 
 template <int K, class TAS, class CB>
-EDV_HD uint32_t verify_phase_dsm_split_point(ge_p3& Q, const uint32_t h[8], const uint32_t S[8], const TAS& tas,
-                                             const CB& cb) {
+EDV_HD void verify_phase_dsm_split_point(ge_p3& Q, const uint32_t h[8], const uint32_t S[8], const TAS& tas,
+                                         const CB& cb) {
   constexpr int kWords = 8 / K;       // recoded words per table
   constexpr int kDigits = 8 * kWords;  // radix-16 digits per table
   uint32_t hy[8];
@@ -250,7 +249,7 @@ EDV_HD uint32_t verify_phase_dsm_split_point(ge_p3& Q, const uint32_t h[8], cons
       ge_add_signed(Q, Q, c, e < 0);
     }
   }
-  return comb_mul_add<kBaseW>(Q, S, cb);
+  comb_mul_add<kBaseW>(Q, S, cb);
 }
 
 // encode(R') == R byte for byte (per-request inversion; the kernels batch it).

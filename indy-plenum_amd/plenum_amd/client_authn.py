@@ -950,7 +950,6 @@ class GpuAuthMixin:
         ks = self._key_store()
         spec, parts = None, None
         if (g.speculate and g.kid_map is not None and ks is not None and _kid_map is not None
-                and os.environ.get("EDV_SPECULATE", "1") != "0"
                 and spans_buf is not None and kid_buf is not None and getattr(eng, "supports_staged_parts", False)):
             # kid_map's ids are usable only while no slot has been reused since it was made: an
             # eviction, a retired slot or a reset (by anyone sharing the engine: _sync sees it)
@@ -967,7 +966,7 @@ class GpuAuthMixin:
                     g.stats["part_failures"] = g.stats.get("part_failures", 0) + 1
                     g.last_part_error = str(ex)
                 if parts is not None:
-                    spec = (g.kid_map, kid_buf, eng.parter(), int(os.environ.get("EDV_PART_ITEMS", _PART_ITEMS)))
+                    spec = (g.kid_map, kid_buf, eng.parter(), _PART_ITEMS)
         t0 = perf_counter()
         try:
             scan = _scan_batch(msgs, [SIG], g.scan_threads, [bufs[0], bufs[1], spans_buf], slot, 2, eng.stager(),
@@ -1199,7 +1198,6 @@ class GpuAuthMixin:
         store change has invalidated (_authenticate_staged's condition)."""
         g = self._g
         if not (g.speculate and g.kid_map is not None and _kid_map is not None
-                and os.environ.get("EDV_SPECULATE", "1") != "0"
                 and getattr(self._engine(), "supports_staged_parts", False)):
             return False
         ks = self._key_store()

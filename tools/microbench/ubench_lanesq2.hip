@@ -118,7 +118,7 @@ __global__ void k_lane(const uint32_t* in, uint32_t* out, int n) {
   for (int i = 0; i < 10; ++i) f.v[i] = in[16 + i];
   if (threadIdx.x == 0) {
 #pragma unroll 1
-    for (int s = 0; s < n; ++s) fe_sq_o<2>(f, f);
+    for (int s = 0; s < n; ++s) fe_sq(f, f);
     for (int i = 0; i < 10; ++i) out[16 + i] = f.v[i];
   }
 }

@@ -76,7 +76,7 @@ __global__ void k_lane(const uint32_t* in, uint32_t* out, long long* t, int n) {
   fe a;
   for (int i = 0; i < 10; ++i) a.v[i] = in[16 + i];
   long long t0 = __builtin_amdgcn_s_memtime();
-  for (int i = 0; i < n; ++i) fe_sq_o<2>(a, a);
+  for (int i = 0; i < n; ++i) fe_sq(a, a);
   long long t1 = __builtin_amdgcn_s_memtime();
   for (int i = 0; i < 10; ++i) out[16 + i] = a.v[i];
   t[1] = t1 - t0;

@@ -98,7 +98,7 @@ __global__ void k_lane(const uint32_t* in, uint32_t* out, long long* t, int n) {
   const long long t0 = __builtin_amdgcn_s_memtime();
   if (threadIdx.x == 0) {
 #pragma unroll 1
-    for (int s = 0; s < n; ++s) fe_sq_o<2>(f, f);
+    for (int s = 0; s < n; ++s) fe_sq(f, f);
   }
   const long long t1 = __builtin_amdgcn_s_memtime();
   if (threadIdx.x == 0) {

@@ -33,10 +33,10 @@ for i in range(n):
     reqs.append(json.loads(json.dumps(r)))
 out = [bytearray(), bytearray()]
 for rep in range(reps):
-    ab = os.environ.get("AB")  # alternate a scan switch off / on (AB=1: EDV_SCAN_PREFETCH; else its name)
+    ab = os.environ.get("AB")  # the name of a scan switch to alternate off / on (e.g. AB=EDV_SCAN_SHAPES)
     if ab:
-        os.environ["EDV_SCAN_PREFETCH" if ab == "1" else ab] = "1" if rep % 2 else "0"
+        os.environ[ab] = "1" if rep % 2 else "0"
     t0 = time.perf_counter()
     H.scan_batch_u(reqs, ["signature"], threads, out, 96)
-    flags = "".join(" %s=%s" % (k[9:].lower(), os.environ.get(k, "1")) for k in ("EDV_SCAN_PREFETCH", "EDV_SCAN_DIRECT"))
+    flags = " %s=%s" % (ab, os.environ[ab]) if ab else ""
     print("scan %d requests, %d threads%s: %.2f ms" % (n, threads, flags, (time.perf_counter() - t0) * 1e3), flush=True)

@@ -1,7 +1,7 @@
 """Host-only A/B of the native scan's switches on configs[1]-shaped requests (each json-decoded on
 its own, as bench.py's end_to_end leg builds them), alternating in one process so the host's load
 affects every variant alike.  usage: python tools/scan_probe.py [n] [threads,...] [reps] [VAR=a/b ...]
-e.g. python tools/scan_probe.py 1000000 1,16 5 EDV_SCAN_SHAPES=1/0 EDV_SCAN_PREFETCH=1/0"""
+e.g. python tools/scan_probe.py 1000000 1,16 5 EDV_SCAN_SHAPES=1/0"""
 import json
 import os
 import sys

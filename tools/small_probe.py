@@ -43,7 +43,7 @@ for i in range(len(msgs)):
 lat = np.array(lat[50:]) * 1e6
 try:
     comb_us = eng.last_phases_ms()[2] * 1e3
-except Exception:  # EDV_SMALL_NOEV=1: the small path records no phase events
+except Exception:  # a single request's small kernel records no phase events
     comb_us = float("nan")
 print("key window %d: engine call n=1 p50 %.1f us p99 %.1f us; phases (comb) %.1f us" % (
     kw, np.percentile(lat, 50), np.percentile(lat, 99), comb_us))
