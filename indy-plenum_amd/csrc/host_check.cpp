@@ -704,3 +704,61 @@ int64_t hc_wire_idents(const uint8_t* text, const uint64_t* off_p, uint64_t n, c
   return (int64_t)rank[n];
 }
 }  // extern "C"
+
+// ---- the CPU twins of tests/native/ed_probe.hip's one-item-per-lane entry points (same
+// signatures, the same calls: csrc/ed_probe_ops.h), for tests/test_ed_edges.py: the tables of
+// tests/ed_edge_common.py through this build's EDV_BOUND_CHECK assertions.
+#include <stdlib.h>
+
+#include "ed_probe_ops.h"
+extern "C" {
+// the base comb's window in this build (kBaseW)
+int edv_host_ed_base_w(void) { return edv::kBaseW; }
+int edv_host_ed_lane_io(int op, int io[2]) {
+  if (op < 0 || op >= edv::edp::kLaneOps) return -1;
+  io[0] = edv::edp::lane_in_words(op);
+  io[1] = edv::edp::lane_out_words(op);
+  return 0;
+}
+int edv_host_ed_lane(int op, const uint32_t* in, uint64_t n, uint32_t* out) {
+  namespace P = edv::edp;
+  if (op < 0 || op >= P::kLaneOps || n > 0x7fffffffull) return -1;
+  if (op == P::kFeSqn)
+    for (uint64_t i = 0; i < n; ++i)
+      if (in[11 * i + 10] < 1 || in[11 * i + 10] > 300) return -1;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint32_t* a = in + (uint64_t)P::lane_in_words(op) * i;
+    uint32_t* o = out + (uint64_t)P::lane_out_words(op) * i;
+    switch (op) {
+#define EDV_CASE(OP) \
+  case OP: P::lane_op<OP>(a, o); break;
+      EDV_ED_LANE_OPS(EDV_CASE)
+#undef EDV_CASE
+    }
+  }
+  return 0;
+}
+// forms 0 and 1 (the wave form is device only: -1)
+int edv_host_ed_hash(int form, const uint8_t* sig64, const uint8_t* pk32, const uint8_t* buf, uint64_t buf_len,
+                     const uint64_t* start, const uint64_t* mlen, uint64_t n, uint32_t* h_out, uint8_t* ok_out) {
+  if (form < 0 || form > 1) return -1;
+  for (uint64_t i = 0; i < n; ++i)
+    if (start[i] > buf_len || mlen[i] > buf_len - start[i]) return -1;
+  const size_t padded = (buf_len + 15) / 16 * 16 + 16;
+  uint8_t* b = (uint8_t*)aligned_alloc(16, padded);  // start[i] mod 16 is the message's alignment
+  if (!b) return -2;
+  memset(b, 0, padded);
+  memcpy(b, buf, buf_len);
+  std::vector<Chunk16> units;
+  for (uint64_t i = 0; i < n; ++i) {
+    uint32_t sig[16], pk[8], h[8];
+    memcpy(sig, sig64 + 64 * i, 64);
+    memcpy(pk, pk32 + 32 * i, 32);
+    units.assign(sha512_units64(mlen[i]), Chunk16{0xdeadbeefu, 0xdeadbeefu, 0xdeadbeefu, 0xdeadbeefu});
+    ok_out[i] = edv::edp::hash_op(form, h, sig, pk, b + start[i], mlen[i], units.data()) ? 1 : 0;
+    memcpy(h_out + 8 * i, h, 32);
+  }
+  free(b);
+  return 0;
+}
+}  // extern "C"
