@@ -383,6 +383,27 @@ int edv_verify_spans_device(edv_ctx *ctx, const void *d_sig64, const void *d_key
  * serializations stay in HBM as the context's "wire batch" until the next edv_wire_scan. */
 int edv_wire_scan(edv_ctx *ctx, const uint8_t *text, const uint64_t *text_off, uint64_t n,
                   uint8_t *status, uint32_t *idr_span);
+/* edv_wire_scan for what a NODE stack receives: message i = text[text_off[i] .. text_off[i+1]) is
+ * a client request, a PROPAGATE or any other node message -- an rxMsgs entry (esc[i] = 0) or the
+ * still-escaped body of one string of a BATCH's "messages" (esc[i] = 1; _hostpack.gather_node_texts
+ * cuts them out).  edv_wire_unwrap_kernel (csrc/wire_unwrap.h, DESIGN.md "Node messages") turns each
+ * into a text the scanner accepts -- the signed request object's bytes in place, spaces elsewhere
+ * -- and the unchanged scan runs over that.  cls[n]: EDV_NODE_REQUEST (status[i] and idr_span say
+ * what the scan made of it), EDV_NODE_HOST (the caller decodes the message; never an error) or
+ * EDV_NODE_NONE (the message holds no signed request); for the last two status[i] is
+ * EDV_WIRE_HOST.  idr_span is relative to the UNWRAPPED text, which stays in HBM
+ * (edv_wire_ident_text reads identifiers out of it).  Leaves the context's wire batch exactly as
+ * edv_wire_scan does: edv_wire_verify / _idents / _verify_idents / _readback follow unchanged. */
+#define EDV_NODE_REQUEST 0
+#define EDV_NODE_HOST    1
+#define EDV_NODE_NONE    2
+int edv_wire_scan_node(edv_ctx *ctx, const uint8_t *text, const uint64_t *text_off, const uint8_t *esc, uint64_t n,
+                       uint8_t *cls, uint8_t *status, uint32_t *idr_span);
+/* The identifier bytes of the wire batch's items uniq_item[0 .. n_uniq) (status 0 each; what
+ * edv_wire_idents returned), gathered on the GPU from the text the scan read: identifier j at
+ * out[out_off[j] .. out_off[j+1]), out_off[n_uniq+1] written here from 0.  out needs room for
+ * the sum of those items' idr_span lengths.  Only the distinct identifiers cross PCIe. */
+int edv_wire_ident_text(edv_ctx *ctx, const uint32_t *uniq_item, uint64_t n_uniq, uint8_t *out, uint64_t *out_off);
 /* Verify the wire batch's status-0 items: key_id[i] = registered key id, or EDV_WIRE_NO_ID
  * (0xffffffff) to use pk32[32*i..] on the general path; EDV_WIRE_SKIP (0xfffffffe) = leave the
  * bit 0 (no key / the host decides).  Same verdicts as edv_verify_batch(_keyed) on the same bytes.

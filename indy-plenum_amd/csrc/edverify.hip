@@ -18,6 +18,8 @@
 //                           ballot into the accept bitmask.
 //   edv_wire_scan_kernel   request texts from the wire -> decoded signatures,
 //                          identifier spans and signing bytes in HBM (wire_scan.h)
+//   edv_wire_unwrap_kernel   node messages (PROPAGATEs, BATCH members) -> texts the scan
+//                          accepts, in front of it (wire_unwrap.h)
 //   edv_wire_ident_insert_kernel / _flag_kernel / _number_kernel   the wire batch's
 //                          distinct identifiers in first-occurrence order and each
 //                          item's index into them (wire_idents.h);
@@ -52,6 +54,7 @@
 #include "verify_core.h"
 #include "wire_idents.h"
 #include "wire_scan.h"
+#include "wire_unwrap.h"
 
 using namespace edv;
 
@@ -727,6 +730,93 @@ __global__ __launch_bounds__(kWireThreads) void edv_wire_scan_kernel(
     __syncthreads();  // every lane has read s_next / s_lo / s_hi and s_out before the next tile resets them
     t0 = next & ~15ull;
   }
+}
+
+// ---- node messages in front of the scan (edverify.h edv_wire_scan_node; the lane code is
+// wire_unwrap.h).  The same tile scheme as edv_wire_scan_kernel, as its own copy of the loop (the
+// scan kernel is left as it is; DESIGN.md "Node messages"): the uploaded bodies `raw` come into
+// LDS with 16-byte loads, every lane whose whole message lies in the tile unwraps it from LDS into
+// the second LDS tile at the same offset -- the request object's bytes in place, ' ' elsewhere,
+// never longer than the message --, and the tile's finished stretch goes out to `text`, the buffer
+// edv_wire_scan_kernel then reads, with 16-byte stores and byte stores at the ragged ends.  Per
+// message its class (wire_unwrap.h); a message over kWireMaxText is the host's, unread.
+__global__ __launch_bounds__(kWireThreads) void edv_wire_unwrap_kernel(
+    const uint8_t* __restrict__ raw, const uint64_t* __restrict__ off, const uint8_t* __restrict__ esc, uint64_t base,
+    uint64_t first, uint64_t end, uint8_t* __restrict__ text, uint8_t* __restrict__ cls) {
+  __shared__ uint4 s_in[kWireTile / 16];
+  __shared__ uint4 s_out[kWireTile / 16];
+  __shared__ unsigned long long s_next, s_lo, s_hi;
+  const uint32_t tid = threadIdx.x;
+  const uint64_t i0 = first + (uint64_t)blockIdx.x * kWireThreads;
+  if (i0 >= end) return;  // (block-uniform)
+  const uint64_t i = i0 + tid;
+  const uint64_t i1 = i0 + kWireThreads < end ? i0 + kWireThreads : end;
+  const bool valid = i < i1;
+  uint64_t a = 0, b = 0;  // this lane's message in the device buffers
+  if (valid) {
+    a = off[i] - base + kWirePad;
+    b = off[i + 1] - base + kWirePad;
+  }
+  const uint64_t load_end = (off[i1] - base + kWirePad + 15) & ~15ull;  // inside the tail
+  bool done = !valid;
+  if (valid && b - a > kWireMaxText) {
+    cls[i] = (uint8_t)kUnwrapHost;
+    done = true;
+  }
+  uint64_t t0 = (off[i0] - base + kWirePad) & ~15ull;
+  for (;;) {
+    if (tid == 0) {
+      s_next = ~0ull;
+      s_lo = ~0ull;
+      s_hi = 0;
+    }
+    for (uint32_t k = tid; k < kWireTile / 16; k += kWireThreads) {
+      const uint64_t p = t0 + 16ull * k;
+      if (p < load_end) s_in[k] = *(const uint4*)(raw + p);
+    }
+    __syncthreads();
+    if (!done && b <= t0 + kWireTile) {  // (a >= t0: the tile starts at or before the first message not done)
+      const uint32_t lo = (uint32_t)(a - t0), len = (uint32_t)(b - a);
+      cls[i] = (uint8_t)wire_unwrap_one((const uint8_t*)s_in + lo, len, (uint32_t)esc[i], (uint8_t*)s_out + lo);
+      done = true;
+      atomicMin(&s_lo, (unsigned long long)a);
+      atomicMax(&s_hi, (unsigned long long)b);
+    }
+    if (!done) atomicMin(&s_next, (unsigned long long)a);
+    __syncthreads();
+    const uint64_t lo = s_lo, hi = s_hi, next = s_next;
+    if (lo < hi) {  // the stretch [lo, hi) of this tile's messages, whole 16-byte pieces wide
+      const uint8_t* so = (const uint8_t*)s_out;
+      const uint64_t wa = (lo + 15) & ~15ull, wb = hi & ~15ull;
+      if (wa <= wb) {
+        for (uint64_t p = lo + tid; p < wa; p += kWireThreads) text[p] = so[p - t0];
+        for (uint64_t p = wa + 16ull * tid; p < wb; p += 16ull * kWireThreads)
+          *(uint4*)(text + p) = s_out[(p - t0) >> 4];
+        for (uint64_t p = wb + tid; p < hi; p += kWireThreads) text[p] = so[p - t0];
+      } else {
+        for (uint64_t p = lo + tid; p < hi; p += kWireThreads) text[p] = so[p - t0];
+      }
+    }
+    if (next == ~0ull) break;
+    __syncthreads();  // every lane has read s_next / s_lo / s_hi and s_out before the next tile resets them
+    t0 = next & ~15ull;
+  }
+}
+
+// The identifier bytes of the items item[0 .. m) of the wire batch, back to back: identifier j at
+// out[at[j] ..) (at = the exclusive sum of the lengths, made on the host from the spans it
+// holds).  One lane per identifier; the spans were checked against their items by the scan.
+__global__ __launch_bounds__(kBlock) void edv_wire_ident_text_kernel(
+    const uint8_t* __restrict__ text, const uint64_t* __restrict__ off, uint64_t base, uint64_t n,
+    const uint32_t* __restrict__ span, const uint32_t* __restrict__ item, const uint64_t* __restrict__ at, uint64_t m,
+    uint8_t* __restrict__ out) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const uint32_t i = item[j];
+  if (i >= n) return;
+  const uint64_t len = at[j + 1] - at[j], a = off[i] - base + span[2 * (uint64_t)i];
+  if (span[2 * (uint64_t)i + 1] != len || a + len > off[i + 1] - base) return;  // (never: checked on the host)
+  for (uint64_t k = 0; k < len; ++k) out[at[j] + k] = text[a + k];
 }
 
 // ---- the wire batch's distinct identifiers (edverify.h edv_wire_idents; the lane code is wire_idents.h)
@@ -1644,6 +1734,10 @@ struct edv_ctx {
   // that is not pinned and for the results; the status bytes kept on the host for the verify
   Buf w_text, w_msg, w_sig, w_spans, w_status, w_idr, w_off, w_keys, w_words;
   Buf wh_text, wh_off, wh_out, wh_keys, wh_bits;
+  // edv_wire_scan_node: the uploaded message bodies (w_text then holds what the unwrap kernel made
+  // of them), the escape flags and the classes; edv_wire_ident_text: its input (items, offsets),
+  // the gathered identifier bytes, pinned staging for both
+  Buf w_raw, w_esc, w_cls, wh_esc, w_itext_in, w_itext, wh_itext;
   uint64_t wire_n = 0, wire_bytes = 0, wire_base = 0;
   bool wire_ok = false;
   // edv_wire_idents: the table (owner [cap] then first [cap]), per item its slot, flag, rank
@@ -3166,13 +3260,16 @@ int edv_verify_staged_subset(edv_ctx* ctx, const uint32_t* idx, const uint8_t* p
 // items per upload + scan launch (the verify's chunks are launch_pipeline's)
 constexpr uint64_t kWireChunk = 1ull << 17;
 
-int edv_wire_scan(edv_ctx* ctx, const uint8_t* text, const uint64_t* text_off, uint64_t n, uint8_t* status,
-                  uint32_t* idr_span) {
+// edv_wire_scan (esc and cls null) and edv_wire_scan_node (node messages: the bodies go up to
+// w_raw, edv_wire_unwrap_kernel writes w_text from them, and the same scan launch follows).
+static int wire_scan_run(edv_ctx* ctx, bool node, const uint8_t* text, const uint64_t* text_off, const uint8_t* esc,
+                         uint64_t n, uint8_t* cls, uint8_t* status, uint32_t* idr_span) {
   int r = set_device(ctx);
   if (r) return r;
   ctx->wire_ok = false;
   ctx->wire_uidx_ok = false;
   if (!text_off || (n && (!status || !idr_span))) return set_err(EDV_EINVAL, "null pointer");
+  if (node && n && (!esc || !cls)) return set_err(EDV_EINVAL, "null pointer");
   if (n >= EDV_WIRE_SKIP) return set_err(EDV_EINVAL, "too many items");
   uint64_t bad = 0;
   for (uint64_t i = 0; i < n; ++i) bad |= (uint64_t)(text_off[i] > text_off[i + 1]);
@@ -3190,8 +3287,17 @@ int edv_wire_scan(edv_ctx* ctx, const uint8_t* text, const uint64_t* text_off, u
   const uint64_t bytes = kWirePad + total + kWireTail;
   if ((r = ensure(ctx->w_text, bytes)) || (r = ensure(ctx->w_msg, bytes)) || (r = ensure(ctx->w_sig, 64 * n)) ||
       (r = ensure(ctx->w_spans, 16 * n)) || (r = ensure(ctx->w_status, n)) || (r = ensure(ctx->w_idr, 8 * n)) ||
-      (r = ensure(ctx->w_off, 8 * (n + 1))) || (r = ensure_pinned(ctx->wh_out, 9 * n)))
+      (r = ensure(ctx->w_off, 8 * (n + 1))) || (r = ensure_pinned(ctx->wh_out, 10 * n)))
     return r;
+  const void* src_esc = esc;
+  if (node) {
+    if ((r = ensure(ctx->w_raw, bytes)) || (r = ensure(ctx->w_esc, n)) || (r = ensure(ctx->w_cls, n))) return r;
+    if (!pinned_range(esc, n)) {
+      if ((r = ensure_pinned(ctx->wh_esc, n))) return r;
+      memcpy(ctx->wh_esc.p, esc, n);
+      src_esc = ctx->wh_esc.p;
+    }
+  }
   const void* src_text = text + base;
   if (total && !pinned_range(src_text, total)) {
     if ((r = ensure_pinned(ctx->wh_text, total))) return r;
@@ -3220,14 +3326,27 @@ int edv_wire_scan(edv_ctx* ctx, const uint8_t* text, const uint64_t* text_off, u
   HIP_TRY(hipMemsetAsync(d_text, 0, kWirePad, cs));
   HIP_TRY(hipMemsetAsync(d_text + kWirePad + total, 0, kWireTail, cs));
   HIP_TRY(hipMemcpyAsync(ctx->w_off.p, src_off, 8 * (n + 1), hipMemcpyHostToDevice, cs));
+  uint8_t* d_up = d_text;  // where the caller's bytes go
+  if (node) {
+    d_up = (uint8_t*)ctx->w_raw.p;
+    HIP_TRY(hipMemsetAsync(d_up, 0, kWirePad, cs));
+    HIP_TRY(hipMemsetAsync(d_up + kWirePad + total, 0, kWireTail, cs));
+    HIP_TRY(hipMemcpyAsync(ctx->w_esc.p, src_esc, n, hipMemcpyHostToDevice, cs));
+  }
   for (uint64_t c0 = 0, c = 0; c0 < n; c0 += kWireChunk, ++c) {
     const uint64_t cn = n - c0 < kWireChunk ? n - c0 : kWireChunk;
     const uint64_t ta = text_off[c0] - base, tb = text_off[c0 + cn] - base;
     if (tb > ta)
-      HIP_TRY(hipMemcpyAsync(d_text + kWirePad + ta, (const uint8_t*)src_text + ta, tb - ta, hipMemcpyHostToDevice,
+      HIP_TRY(hipMemcpyAsync(d_up + kWirePad + ta, (const uint8_t*)src_text + ta, tb - ta, hipMemcpyHostToDevice,
                              cs));
     HIP_TRY(hipEventRecord(ctx->wire_ev[c], cs));
     HIP_TRY(hipStreamWaitEvent(st, ctx->wire_ev[c], 0));
+    if (node) {
+      hipLaunchKernelGGL(edv_wire_unwrap_kernel, dim3((uint32_t)div_up(cn, kWireThreads)), dim3(kWireThreads), 0, st,
+                         (const uint8_t*)d_up, (const uint64_t*)ctx->w_off.p, (const uint8_t*)ctx->w_esc.p, base, c0,
+                         c0 + cn, d_text, (uint8_t*)ctx->w_cls.p);
+      HIP_TRY(hipGetLastError());
+    }
     hipLaunchKernelGGL(edv_wire_scan_kernel, dim3((uint32_t)div_up(cn, kWireThreads)), dim3(kWireThreads), 0, st,
                        (const uint8_t*)d_text, (const uint64_t*)ctx->w_off.p, base, c0, c0 + cn, n,
                        (uint8_t*)ctx->w_msg.p, (uint8_t*)ctx->w_sig.p, (uint8_t*)ctx->w_status.p,
@@ -3237,12 +3356,24 @@ int edv_wire_scan(edv_ctx* ctx, const uint8_t* text, const uint64_t* text_off, u
   uint8_t* h = (uint8_t*)ctx->wh_out.p;  // identifier spans, then the status bytes
   HIP_TRY(hipMemcpyAsync(h, ctx->w_idr.p, 8 * n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(h + 8 * n, ctx->w_status.p, n, hipMemcpyDeviceToHost, st));
+  if (node) HIP_TRY(hipMemcpyAsync(h + 9 * n, ctx->w_cls.p, n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   memcpy(idr_span, h, 8 * n);
   memcpy(status, h + 8 * n, n);
   memcpy(ctx->wire_status.data(), h + 8 * n, n);
+  if (node) memcpy(cls, h + 9 * n, n);
   ctx->wire_ok = true;
   return 0;
+}
+
+int edv_wire_scan(edv_ctx* ctx, const uint8_t* text, const uint64_t* text_off, uint64_t n, uint8_t* status,
+                  uint32_t* idr_span) {
+  return wire_scan_run(ctx, false, text, text_off, nullptr, n, nullptr, status, idr_span);
+}
+
+int edv_wire_scan_node(edv_ctx* ctx, const uint8_t* text, const uint64_t* text_off, const uint8_t* esc, uint64_t n,
+                       uint8_t* cls, uint8_t* status, uint32_t* idr_span) {
+  return wire_scan_run(ctx, true, text, text_off, esc, n, cls, status, idr_span);
 }
 
 // The items idx[0 .. m) of the wire batch (status 0) on one path: their signatures and spans
@@ -3409,6 +3540,50 @@ int edv_wire_idents(edv_ctx* ctx, uint32_t* uidx, uint32_t* uniq_item, uint64_t*
   ctx->wire_nu = nu;
   ctx->wire_uidx_ok = true;
   *n_uniq = nu;
+  return 0;
+}
+
+int edv_wire_ident_text(edv_ctx* ctx, const uint32_t* uniq_item, uint64_t n_uniq, uint8_t* out, uint64_t* out_off) {
+  int r = set_device(ctx);
+  if (r) return r;
+  if (!ctx->wire_ok) return set_err(EDV_EINVAL, "no wire batch (edv_wire_scan first)");
+  if (!out_off) return set_err(EDV_EINVAL, "null pointer");
+  out_off[0] = 0;
+  if (n_uniq == 0) return 0;
+  const uint64_t n = ctx->wire_n;
+  if (!uniq_item) return set_err(EDV_EINVAL, "null pointer");
+  if (n_uniq > n) return set_err(EDV_EINVAL, "more identifiers than items");
+  // the identifier spans as the scan left them in its pinned result block (kept until the next scan)
+  const uint32_t* span = (const uint32_t*)ctx->wh_out.p;
+  const uint8_t* status = ctx->wire_status.data();
+  for (uint64_t j = 0; j < n_uniq; ++j) {
+    const uint32_t i = uniq_item[j];
+    if (i >= n || status[i] != EDV_WIRE_OK) return set_err(EDV_EINVAL, "identifier %llu: not a scanned item", (unsigned long long)j);
+    out_off[j + 1] = out_off[j] + span[2 * (uint64_t)i + 1];
+  }
+  const uint64_t total = out_off[n_uniq];
+  if (total && !out) return set_err(EDV_EINVAL, "null pointer");
+  if (total > ctx->wire_bytes) return set_err(EDV_EINVAL, "identifier spans outside the batch");
+  const uint64_t in_bytes = 4 * n_uniq + 8 * (n_uniq + 1) + 4;  // items (padded to 8), offsets
+  const uint64_t at_pos = (4 * n_uniq + 7) & ~7ull;
+  if ((r = ensure(ctx->w_itext_in, in_bytes)) || (r = ensure(ctx->w_itext, total)) ||
+      (r = ensure_pinned(ctx->wh_itext, in_bytes + total)))
+    return r;
+  uint8_t* h = (uint8_t*)ctx->wh_itext.p;
+  memcpy(h, uniq_item, 4 * n_uniq);
+  memcpy(h + at_pos, out_off, 8 * (n_uniq + 1));
+  hipStream_t st = ctx->stream;
+  uint8_t* d_in = (uint8_t*)ctx->w_itext_in.p;
+  HIP_TRY(hipMemcpyAsync(d_in, h, at_pos + 8 * (n_uniq + 1), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(edv_wire_ident_text_kernel, dim3((uint32_t)div_up(n_uniq, kBlock)), dim3(kBlock), 0, st,
+                     (const uint8_t*)ctx->w_text.p + kWirePad, (const uint64_t*)ctx->w_off.p, ctx->wire_base, n,
+                     (const uint32_t*)ctx->w_idr.p, (const uint32_t*)d_in, (const uint64_t*)(d_in + at_pos), n_uniq,
+                     (uint8_t*)ctx->w_itext.p);
+  HIP_TRY(hipGetLastError());
+  uint8_t* h_out = h + in_bytes;
+  if (total) HIP_TRY(hipMemcpyAsync(h_out, ctx->w_itext.p, total, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (total) memcpy(out, h_out, total);
   return 0;
 }
 
@@ -3691,7 +3866,8 @@ void edv_destroy(edv_ctx* ctx) {
                           &ctx->w_idr, &ctx->w_off, &ctx->w_keys, &ctx->w_words, &ctx->wh_text, &ctx->wh_off,
                           &ctx->wh_out, &ctx->wh_keys, &ctx->wh_bits, &ctx->w_itab, &ctx->w_islot, &ctx->w_iflag,
                           &ctx->w_irank, &ctx->w_uidx, &ctx->w_uitem, &ctx->w_itmp, &ctx->w_ibad, &ctx->w_ikid,
-                          &ctx->wh_idents, &ctx->wh_ikid})
+                          &ctx->wh_idents, &ctx->wh_ikid, &ctx->w_raw, &ctx->w_esc, &ctx->w_cls, &ctx->wh_esc,
+                          &ctx->w_itext_in, &ctx->w_itext, &ctx->wh_itext})
     free_buf(*b);
   for (int k = 0; k < edv_ctx::kSets; ++k) {
     for (edv_ctx::Buf* b : {&ctx->d_stage_set[k], &ctx->d_spans[k], &ctx->s_sig[k], &ctx->s_key[k], &ctx->s_bits[k],

@@ -627,6 +627,30 @@ void hc_wire_scan(const uint8_t* text, const uint64_t* off, uint64_t n, uint8_t*
 }
 }  // extern "C"
 
+// ---- the node-message unwrap (wire_unwrap.h, the code of edv_wire_unwrap_kernel's lanes) on the
+// CPU, every read and write asserted inside the message's own span, for tests/test_wire_unwrap.py.
+#include "wire_unwrap.h"
+extern "C" {
+// n messages (message i = text[off[i] .. off[i + 1]), esc[i] = 1: a JSON string body): cls[n]
+// (0 request, 1 the host decides, 2 no signed request) and message i's unwrapped text at
+// out[off[i] - off[0] ..) (out holds off[n] - off[0] bytes; spaces for a message over kWireMaxText,
+// which the lane code leaves unread).
+void hc_wire_unwrap(const uint8_t* text, const uint64_t* off, const uint8_t* esc, uint64_t n, uint8_t* cls,
+                    uint8_t* out) {
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t len = off[i + 1] - off[i];
+    uint8_t* o = out + (off[i] - off[0]);
+    if (len > kWireMaxText) {
+      memset(o, ' ', (size_t)len);
+      cls[i] = (uint8_t)kUnwrapHost;
+      continue;
+    }
+    cls[i] = (uint8_t)wire_unwrap_one(CheckedText{text + off[i], (uint32_t)len}, (uint32_t)len, esc[i],
+                                      CheckedOut{o, (uint32_t)len});
+  }
+}
+}  // extern "C"
+
 // ---- the wire batch's distinct identifiers (wire_idents.h, the code of edv_wire_ident_*_kernel's
 // lanes) on the CPU, every read and write asserted in bounds, for tests/test_wire_idents.py.
 #include "wire_idents.h"

@@ -24,6 +24,7 @@
 #include <Python.h>
 
 #include "host_pool.h"
+#include "node_split.h"
 #include <pthread.h>
 #include <emmintrin.h>
 #include <sched.h>
@@ -3733,7 +3734,116 @@ PyObject* py_wire_idents(PyObject*, PyObject* args) {
   return r;
 }
 
+// ---- node messages (authenticate_node_wire_batch): the rxMsgs entries of a node stack split into
+// messages for edv_wire_scan_node; the BATCH parse is node_split.h.
+using edv::NodeSpan;
+using edv::node_split;
+
+// gather_node_texts(entries, out, threads=0) -> (off, esc, entry) with the messages of the n bytes
+// objects of the list copied back to back into the writable buffer `out`: off = uint64 LE[m + 1]
+// from 0, esc = uint8[m] (1: the body of a BATCH member, still escaped; 0: an entry copied whole),
+// entry = uint32 LE[m], ascending, the entry each message came from.  None: not a list, an entry
+// that is not exactly bytes, or out too small.
+PyObject* py_gather_node_texts(PyObject*, PyObject* args) {
+  PyObject* list;
+  Py_buffer bo;
+  int threads = 0;
+  if (!PyArg_ParseTuple(args, "Ow*|i", &list, &bo, &threads)) return nullptr;
+  struct Rel {
+    Py_buffer* a;
+    ~Rel() { PyBuffer_Release(a); }
+  } rel{&bo};
+  if (!PyList_CheckExact(list)) Py_RETURN_NONE;
+  const Py_ssize_t n = PyList_GET_SIZE(list);
+  if ((uint64_t)n >= 0xffffffffull) Py_RETURN_NONE;
+  PyObject** items = ((PyListObject*)list)->ob_item;
+  constexpr Py_ssize_t kChunk = 256;
+  constexpr uint32_t kWhole = 0xffffffffu;
+  const Py_ssize_t nchunks = (n + kChunk - 1) / kChunk;
+  std::vector<std::vector<NodeSpan>> spans((size_t)nchunks);
+  std::vector<uint32_t> members((size_t)n);  // per entry: its members, kWhole = copied whole
+  std::vector<uint64_t> msg_at((size_t)nchunks + 1, 0), byte_at((size_t)nchunks + 1, 0);
+  std::atomic<int> bad{0};
+  const int t = scan_threads(n * 8, threads);
+  run_chunks(n, t, [&](int, Py_ssize_t a, Py_ssize_t b) {
+    std::vector<NodeSpan>& sp = spans[(size_t)(a / kChunk)];
+    uint64_t msgs = 0, bytes = 0;
+    for (Py_ssize_t i = a; i < b; ++i) {
+      if (!PyBytes_CheckExact(items[i])) {
+        bad = 1;
+        return;
+      }
+      const size_t len = (size_t)PyBytes_GET_SIZE(items[i]), before = sp.size();
+      if (node_split((const uint8_t*)PyBytes_AS_STRING(items[i]), len, sp)) {
+        members[(size_t)i] = (uint32_t)(sp.size() - before);
+        msgs += sp.size() - before;
+        for (size_t j = before; j < sp.size(); ++j) bytes += sp[j].len;
+      } else {
+        members[(size_t)i] = kWhole;
+        msgs += 1;
+        bytes += len;
+      }
+    }
+    msg_at[(size_t)(a / kChunk) + 1] = msgs;
+    byte_at[(size_t)(a / kChunk) + 1] = bytes;
+  }, kChunk);
+  if (bad) Py_RETURN_NONE;
+  for (Py_ssize_t c = 0; c < nchunks; ++c) {
+    msg_at[(size_t)c + 1] += msg_at[(size_t)c];
+    byte_at[(size_t)c + 1] += byte_at[(size_t)c];
+  }
+  const uint64_t m = msg_at[(size_t)nchunks];
+  if (byte_at[(size_t)nchunks] > (uint64_t)bo.len || m >= 0xffffffffull) Py_RETURN_NONE;
+  PyObject* off_o = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)((m + 1) * 8));
+  PyObject* esc_o = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)m);
+  PyObject* ent_o = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)(m * 4));
+  if (!off_o || !esc_o || !ent_o) {
+    Py_XDECREF(off_o);
+    Py_XDECREF(esc_o);
+    Py_XDECREF(ent_o);
+    return nullptr;
+  }
+  uint64_t* off = (uint64_t*)PyBytes_AS_STRING(off_o);
+  uint8_t* esc = (uint8_t*)PyBytes_AS_STRING(esc_o);
+  uint32_t* ent = (uint32_t*)PyBytes_AS_STRING(ent_o);
+  char* dst = (char*)bo.buf;
+  off[m] = byte_at[(size_t)nchunks];
+  run_chunks(n, t, [&](int, Py_ssize_t a, Py_ssize_t b) {
+    const std::vector<NodeSpan>& sp = spans[(size_t)(a / kChunk)];
+    uint64_t k = msg_at[(size_t)(a / kChunk)], at = byte_at[(size_t)(a / kChunk)];
+    size_t j = 0;
+    for (Py_ssize_t i = a; i < b; ++i) {
+      const char* src = PyBytes_AS_STRING(items[i]);
+      if (members[(size_t)i] == kWhole) {
+        const size_t len = (size_t)PyBytes_GET_SIZE(items[i]);
+        off[k] = at;
+        esc[k] = 0;
+        ent[k++] = (uint32_t)i;
+        memcpy(dst + at, src, len);
+        at += len;
+        continue;
+      }
+      for (const size_t end = j + members[(size_t)i]; j < end; ++j) {
+        off[k] = at;
+        esc[k] = 1;
+        ent[k++] = (uint32_t)i;
+        memcpy(dst + at, src + sp[j].at, (size_t)sp[j].len);
+        at += sp[j].len;
+      }
+    }
+  }, kChunk);
+  PyObject* r = PyTuple_Pack(3, off_o, esc_o, ent_o);
+  Py_DECREF(off_o);
+  Py_DECREF(esc_o);
+  Py_DECREF(ent_o);
+  return r;
+}
+
 PyMethodDef kMethods[] = {
+    {"gather_node_texts", py_gather_node_texts, METH_VARARGS,
+     "gather_node_texts(entries, out, threads=0) -> (off_u64, esc_u8, entry_u32) with the entries' messages (a "
+     "strictly parsed BATCH's member bodies, any other entry whole) copied back to back into the writable buffer "
+     "out, or None (not a list of bytes, or out too small)"},
     {"gather_texts", py_gather_texts, METH_VARARGS,
      "gather_texts(texts, out, threads=0) -> offsets (uint64 LE, n + 1) with the list's bytes copied back to back "
      "into the writable buffer out, or None (not a list of bytes, or out too small)"},

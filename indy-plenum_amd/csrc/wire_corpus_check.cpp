@@ -7,8 +7,14 @@
 // (wire_idents.h, the lane code of edv_wire_ident_*_kernel) with a table of 2 n slots and again
 // with one just large enough, whose chains wrap.
 //
+// --node: the corpus is rxMsgs entries of a node stack.  Every entry, in a heap block of exactly
+// its length, goes through the BATCH parse (node_split.h); every message that yields -- a member
+// body, or the entry whole -- is copied into a block of exactly its length and unwrapped
+// (wire_unwrap.h, the lane code of edv_wire_unwrap_kernel) into another, and the result is
+// scanned.  Every entry is also unwrapped whole both as plain text and as an escaped body.
+//
 // Corpus file: per text a little-endian uint32 length, then the bytes
-// (tools/wire_probe.py --write-corpus FILE writes the test corpus in this form).
+// (tools/wire_probe.py --write-corpus FILE / --write-node-corpus FILE write the test corpora).
 // Prints the counts; exit status 0 unless the file is malformed.
 #include <stdint.h>
 #include <stdio.h>
@@ -17,8 +23,10 @@
 
 #include <vector>
 
+#include "node_split.h"
 #include "wire_idents.h"
 #include "wire_scan.h"
+#include "wire_unwrap.h"
 
 namespace {
 struct SerialTable {  // the device's atomics, one item at a time
@@ -59,17 +67,102 @@ long idents(const uint8_t* text, const std::vector<uint64_t>& off, const std::ve
   free(slot);
   return nu;
 }
+// One message through the unwrap and the scan, each buffer a heap block of exactly len bytes.
+struct NodeCounts {
+  uint64_t cls[3] = {0, 0, 0}, scanned = 0;
+};
+bool unwrap_message(const uint8_t* body, uint32_t len, uint32_t esc, NodeCounts& c) {
+  uint8_t* text = (uint8_t*)malloc(len ? len : 1);
+  uint8_t* mid = (uint8_t*)malloc(len ? len : 1);
+  uint8_t* out = (uint8_t*)malloc(len ? len : 1);
+  memcpy(text, body, len);
+  const int cls = edv::wire_unwrap_one((const uint8_t*)text, len, esc, mid);
+  bool ok = cls >= 0 && cls <= 2;
+  if (ok) {
+    ++c.cls[cls];
+    if (len <= edv::kWireMaxText) {
+      edv::WireItem it;
+      memset(&it, 0, sizeof it);
+      const int st = edv::wire_scan_one((const uint8_t*)mid, len, out, it);
+      if (st == edv::kWireOk) {
+        ++c.scanned;
+        ok = cls == edv::kUnwrapRequest && it.msg_len <= len && (uint64_t)it.idr_start + it.idr_len <= len;
+      }
+    }
+  }
+  free(text);
+  free(mid);
+  free(out);
+  return ok;
+}
+
+int node_main(FILE* f) {
+  uint64_t entries = 0, split = 0, messages = 0;
+  NodeCounts as_cut, whole, escaped;
+  for (;;) {
+    uint8_t hdr[4];
+    const size_t got = fread(hdr, 1, 4, f);
+    if (got == 0) break;
+    if (got != 4) {
+      fprintf(stderr, "truncated length\n");
+      return 1;
+    }
+    const uint32_t len = (uint32_t)hdr[0] | (uint32_t)hdr[1] << 8 | (uint32_t)hdr[2] << 16 | (uint32_t)hdr[3] << 24;
+    if (len > (64u << 20)) {
+      fprintf(stderr, "implausible length %u\n", len);
+      return 1;
+    }
+    uint8_t* entry = (uint8_t*)malloc(len ? len : 1);
+    if (!entry || fread(entry, 1, len, f) != len) {
+      fprintf(stderr, "truncated entry\n");
+      return 1;
+    }
+    ++entries;
+    std::vector<edv::NodeSpan> spans;
+    bool ok = true;
+    if (edv::node_split(entry, len, spans)) {
+      ++split;
+      for (const edv::NodeSpan& s : spans) {
+        ok = ok && s.at + s.len <= len && unwrap_message(entry + s.at, (uint32_t)s.len, 1, as_cut);
+        ++messages;
+      }
+    } else {
+      ok = spans.empty() && unwrap_message(entry, len, 0, as_cut);
+      ++messages;
+    }
+    ok = ok && unwrap_message(entry, len, 0, whole) && unwrap_message(entry, len, 1, escaped);
+    free(entry);
+    if (!ok) {
+      fprintf(stderr, "entry %llu: a result outside its message\n", (unsigned long long)entries);
+      return 1;
+    }
+  }
+  printf("entries %llu split %llu messages %llu\n", (unsigned long long)entries, (unsigned long long)split,
+         (unsigned long long)messages);
+  const NodeCounts* rows[3] = {&as_cut, &whole, &escaped};
+  const char* names[3] = {"as cut", "entries whole", "entries as escaped bodies"};
+  for (int k = 0; k < 3; ++k)
+    printf("%s: request %llu host %llu none %llu scanned %llu\n", names[k], (unsigned long long)rows[k]->cls[0],
+           (unsigned long long)rows[k]->cls[1], (unsigned long long)rows[k]->cls[2], (unsigned long long)rows[k]->scanned);
+  return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc != 2) {
-    fprintf(stderr, "usage: %s CORPUS\n", argv[0]);
+  const bool node = argc == 3 && strcmp(argv[1], "--node") == 0;
+  if (argc != 2 && !node) {
+    fprintf(stderr, "usage: %s [--node] CORPUS\n", argv[0]);
     return 2;
   }
-  FILE* f = fopen(argv[1], "rb");
+  FILE* f = fopen(argv[argc - 1], "rb");
   if (!f) {
-    perror(argv[1]);
+    perror(argv[argc - 1]);
     return 2;
+  }
+  if (node) {
+    const int r = node_main(f);
+    fclose(f);
+    return r;
   }
   uint64_t texts = 0, scanned = 0, host = 0, out_bytes = 0;
   std::vector<uint8_t> all, status;

@@ -98,6 +98,11 @@ try:  # the wire path's host share: the texts into one pinned buffer, the batch'
 except ImportError:  # pragma: no cover
     _gather_texts = _wire_idents = None
 
+try:  # the node wire path's host share: BATCH entries split into their member bodies
+    from ._hostpack import gather_node_texts as _gather_node_texts
+except ImportError:  # pragma: no cover
+    _gather_node_texts = None
+
 try:  # native packing (csrc/hostpack.cpp)
     from ._hostpack import pack_sm as _pack_sm, pack_split64 as _pack_split64
 except ImportError:  # pragma: no cover - same layout in Python
@@ -340,6 +345,7 @@ class _GpuState:
         self.stats = {"batches": 0, "batch_items": 0, "cache_hits": 0, "single_verifies": 0, "keyed_items": 0,
                       "keys_registered": 0, "prefetched": 0, "wire_items": 0, "wire_host_items": 0}
         self.wire_bytes_per_item = 400.0  # sizes the next wire batch's pinned text buffer
+        self.node_wire_bytes_per_entry = 4096.0  # ... and the next node wire batch's
         self.last_wire_breakdown = None  # the last wire batch's phases (ms)
         # the wire batch's distinct identifiers on the GPU (engine.wire_idents, on an engine with
         # supports_wire_idents); EDV_WIRE_IDENTS=0: the host pass (_hostpack.wire_idents), for A/B runs
@@ -1672,94 +1678,7 @@ class GpuAuthMixin:
             else:
                 uidx_b, uniq = _wire_idents(buf, off_b, status, span, g.scan_threads)
                 uidx = np.frombuffer(uidx_b, np.uint32)
-            nu = len(uniq)
-            ukeys = self._keys_for(uniq)  # authenticate():93-99, once per identifier
-            # per distinct identifier (one more for the items the scan left to the host): 0 = a
-            # 32-byte key (verified), 1 = no key (the verify fails), 2 = exception, 3 = the host decides
-            cls_u = np.full(nu + 1, 3, np.uint8)
-            kid_u = np.full(nu + 1, eng.WIRE_SKIP, np.uint32)
-            keys32 = []
-            for j, k in enumerate(ukeys):
-                if k.__class__ is bytes:
-                    if len(k) == 32:
-                        cls_u[j] = 0
-                        keys32.append(k)
-                    elif not k:
-                        cls_u[j] = 1
-                elif k is None:
-                    cls_u[j] = 1
-                elif isinstance(k, Exception):
-                    cls_u[j] = 2
-            id_of = {}
-            ks = self._key_store()
-            if ks is not None and keys32:
-                uniq_keys = list(dict.fromkeys(keys32))
-                self._register_waiting(ks, uniq_keys)
-                id_of = {k: i for k, i in zip(uniq_keys, ks.lookup(uniq_keys)) if i is not None}
-            general_u = []
-            for j in np.flatnonzero(cls_u[:nu] == 0).tolist():
-                i = id_of.get(ukeys[j])
-                if i is None:
-                    general_u.append(j)
-                    kid_u[j] = eng.WIRE_NO_ID
-                else:
-                    kid_u[j] = i
-            steady = not general_u and not status.any() and not cls_u[:nu].any()
-            if on_gpu and steady:
-                key_id = None  # (the GPU gathers the per-item ids from kid_u)
-            else:
-                # (one native pass: numpy's fancy indexing widens the index array to intp first)
-                key_id = np.frombuffer(_gather_u32(kid_u.tobytes(), uidx_b), np.uint32) if _gather_u32 is not None \
-                    else kid_u[uidx]
-            pk32 = None
-            if general_u:
-                pk_u = np.zeros((nu + 1, 32), np.uint8)
-                pk_u[general_u] = np.frombuffer(b"".join(ukeys[j] for j in general_u), np.uint8).reshape(-1, 32)
-                pk32 = pk_u[uidx]
-            if steady:
-                # every text scanned, every identifier's key registered (the node's steady state):
-                # no per-item class array
-                t3 = _perf_counter()
-                ok = eng.wire_verify_idents(kid_u[:nu]) if on_gpu else eng.wire_verify(key_id, None)
-                t4 = _perf_counter()
-                g.stats["batches"] += 1
-                g.stats["batch_items"] += n
-                g.stats["keyed_items"] += n
-                g.stats["wire_items"] += n
-                failed = np.flatnonzero(~ok)
-                fails = _invalid_signatures(len(failed))
-                results = _results_from(ok.view(np.uint8).tobytes(), uidx_b, uniq)
-                for i, e in zip(failed.tolist(), fails):
-                    results[i] = e
-                t5 = _perf_counter()
-                g.last_wire_breakdown = {"gather": (t1 - t0) * 1e3, "scan": (t2 - t1) * 1e3, "keys": (t3 - t2) * 1e3,
-                                         "verify": (t4 - t3) * 1e3, "results": (t5 - t4) * 1e3,
-                                         "items": n, "host_items": 0}
-                return results
-            icls = cls_u[uidx]
-            t3 = _perf_counter()
-            n_verify = int(np.count_nonzero(icls == 0))
-            ok = eng.wire_verify(key_id, pk32) if n_verify else np.zeros(n, bool)
-            t4 = _perf_counter()
-            if n_verify:
-                g.stats["batches"] += 1
-                g.stats["batch_items"] += n_verify
-                g.stats["keyed_items"] += int(np.count_nonzero(key_id < eng.WIRE_SKIP))
-            if general_u:  # general-path keys earn a slot by verified requests
-                verified_u = np.bincount(uidx[ok], minlength=nu + 1)
-                per_key = {}
-                for j in general_u:
-                    if verified_u[j]:
-                        per_key[ukeys[j]] = per_key.get(ukeys[j], 0) + int(verified_u[j])
-                self._count_verified_keys(list(per_key), list(per_key.values()))
-            failed = np.flatnonzero((icls <= 1) & ~ok)
-            fails = _invalid_signatures(len(failed))
-            results = _results_from(ok.view(np.uint8).tobytes(), uidx_b, uniq)  # the identifier where verified
-            for i, e in zip(failed.tolist(), fails):
-                results[i] = e
-            for i in np.flatnonzero(icls == 2).tolist():
-                results[i] = self._fresh(ukeys[uidx[i]])
-            host = np.flatnonzero(icls == 3).tolist()
+            results, host, t3, t4 = self._wire_verdicts(eng, n, status, uidx, uidx_b, uniq, on_gpu)
             g.stats["wire_items"] += n - len(host)
             if host:
                 self._wire_decoded(texts, host, results)
@@ -1768,6 +1687,224 @@ class GpuAuthMixin:
                                      "verify": (t4 - t3) * 1e3, "results": (t5 - t4) * 1e3,
                                      "items": n, "host_items": len(host)}
             return results
+
+    def _wire_verdicts(self, eng, n, status, uidx, uidx_b, uniq, on_gpu):
+        """The scanned wire batch's results: (results[n] -- the identifier, or the
+        exception instance; None for the items the host decides --, those items'
+        indices, the times before and after the verify)."""
+        import numpy as np
+        g = self._g
+        nu = len(uniq)
+        ukeys = self._keys_for(uniq)  # authenticate():93-99, once per identifier
+        # per distinct identifier (one more for the items the scan left to the host): 0 = a
+        # 32-byte key (verified), 1 = no key (the verify fails), 2 = exception, 3 = the host decides
+        cls_u = np.full(nu + 1, 3, np.uint8)
+        kid_u = np.full(nu + 1, eng.WIRE_SKIP, np.uint32)
+        keys32 = []
+        for j, k in enumerate(ukeys):
+            if k.__class__ is bytes:
+                if len(k) == 32:
+                    cls_u[j] = 0
+                    keys32.append(k)
+                elif not k:
+                    cls_u[j] = 1
+            elif k is None:
+                cls_u[j] = 1
+            elif isinstance(k, Exception):
+                cls_u[j] = 2
+        id_of = {}
+        ks = self._key_store()
+        if ks is not None and keys32:
+            uniq_keys = list(dict.fromkeys(keys32))
+            self._register_waiting(ks, uniq_keys)
+            id_of = {k: i for k, i in zip(uniq_keys, ks.lookup(uniq_keys)) if i is not None}
+        general_u = []
+        for j in np.flatnonzero(cls_u[:nu] == 0).tolist():
+            i = id_of.get(ukeys[j])
+            if i is None:
+                general_u.append(j)
+                kid_u[j] = eng.WIRE_NO_ID
+            else:
+                kid_u[j] = i
+        steady = not general_u and not status.any() and not cls_u[:nu].any()
+        if on_gpu and steady:
+            key_id = None  # (the GPU gathers the per-item ids from kid_u)
+        else:
+            # (one native pass: numpy's fancy indexing widens the index array to intp first)
+            key_id = np.frombuffer(_gather_u32(kid_u.tobytes(), uidx_b), np.uint32) if _gather_u32 is not None \
+                else kid_u[uidx]
+        pk32 = None
+        if general_u:
+            pk_u = np.zeros((nu + 1, 32), np.uint8)
+            pk_u[general_u] = np.frombuffer(b"".join(ukeys[j] for j in general_u), np.uint8).reshape(-1, 32)
+            pk32 = pk_u[uidx]
+        if steady:
+            # every text scanned, every identifier's key registered (the node's steady state):
+            # no per-item class array
+            t3 = _perf_counter()
+            ok = eng.wire_verify_idents(kid_u[:nu]) if on_gpu else eng.wire_verify(key_id, None)
+            t4 = _perf_counter()
+            g.stats["batches"] += 1
+            g.stats["batch_items"] += n
+            g.stats["keyed_items"] += n
+            failed = np.flatnonzero(~ok)
+            fails = _invalid_signatures(len(failed))
+            results = _results_from(ok.view(np.uint8).tobytes(), uidx_b, uniq)
+            for i, e in zip(failed.tolist(), fails):
+                results[i] = e
+            return results, [], t3, t4
+        icls = cls_u[uidx]
+        t3 = _perf_counter()
+        n_verify = int(np.count_nonzero(icls == 0))
+        ok = eng.wire_verify(key_id, pk32) if n_verify else np.zeros(n, bool)
+        t4 = _perf_counter()
+        if n_verify:
+            g.stats["batches"] += 1
+            g.stats["batch_items"] += n_verify
+            g.stats["keyed_items"] += int(np.count_nonzero(key_id < eng.WIRE_SKIP))
+        if general_u:  # general-path keys earn a slot by verified requests
+            verified_u = np.bincount(uidx[ok], minlength=nu + 1)
+            per_key = {}
+            for j in general_u:
+                if verified_u[j]:
+                    per_key[ukeys[j]] = per_key.get(ukeys[j], 0) + int(verified_u[j])
+            self._count_verified_keys(list(per_key), list(per_key.values()))
+        failed = np.flatnonzero((icls <= 1) & ~ok)
+        fails = _invalid_signatures(len(failed))
+        results = _results_from(ok.view(np.uint8).tobytes(), uidx_b, uniq)  # the identifier where verified
+        for i, e in zip(failed.tolist(), fails):
+            results[i] = e
+        for i in np.flatnonzero(icls == 2).tolist():
+            results[i] = self._fresh(ukeys[uidx[i]])
+        return results, np.flatnonzero(icls == 3).tolist(), t3, t4
+
+    # -- node messages from the wire --------------------------------------------------
+    def authenticate_node_wire_batch(self, entries):
+        """authenticate_wire_batch for a NODE stack's drain: entries is a list of
+        bytes, each one rxMsgs text -- a client request, a PROPAGATE, a BATCH of
+        such, or any other node message.  Returns a list of lists: out[e] holds
+        the results for the signed requests inside entry e, in order.  Flattened
+        it is, element for element, authenticate_batch(
+        batching.requests_in_drain(entries)) -- the identifier, or the exception
+        instance (same class, args and __cause__ class); an entry or BATCH member
+        json.loads rejects contributes nothing.
+
+        The host cuts the member strings out of each BATCH
+        (_hostpack.gather_node_texts) and copies the bodies into pinned memory;
+        the GPU unescapes them, finds the request inside a PROPAGATE
+        (edv_wire_unwrap_kernel, csrc/wire_unwrap.h) and scans and verifies it
+        as authenticate_wire_batch does.  Messages outside that grammar (a
+        nested BATCH, a \\u escape, a float in the envelope, ...) are decoded
+        here and go through authenticate_batch in one call.  getVerkey is
+        called once per distinct identifier of the GPU-handled items, in
+        first-occurrence order; the verify-ahead cache is neither read nor
+        filled.  An engine without the node wire path (a MultiEngine, a test
+        double) takes the host definition for the whole call."""
+        was = gc.isenabled()
+        gc.disable()
+        try:
+            eng = self._engine()
+            if (_gather_node_texts is not None and self._native_host_steps()
+                    and getattr(eng, "supports_wire_node", False) and getattr(eng, "supports_wire_idents", False)
+                    and entries.__class__ is list):
+                res = self._authenticate_node_wire(entries, eng)
+                if res is not None:
+                    return res
+            return self._node_wire_decoded(entries)
+        finally:
+            if was:
+                gc.enable()
+
+    def _node_wire_decoded(self, entries):
+        """The host definition: requests_in_drain per entry, one authenticate_batch."""
+        from .batching import requests_in_drain
+        per_entry = [requests_in_drain([e]) for e in entries]
+        flat = [r for reqs in per_entry for r in reqs]
+        res = iter(self.authenticate_batch(flat) if flat else ())
+        self._g.stats["wire_host_items"] += len(per_entry)
+        return [[next(res) for _ in reqs] for reqs in per_entry]
+
+    def _authenticate_node_wire(self, entries, eng):
+        """The node drain on the GPU; None when entries is not a list of bytes."""
+        import numpy as np
+        g = self._g
+        n_e = len(entries)
+        if n_e == 0:
+            return []
+        with _engine_lock(eng):
+            t0 = _perf_counter()
+            buf = self._wire_text_buffer(eng, int(n_e * g.node_wire_bytes_per_entry) + 4096)
+            got = _gather_node_texts(entries, buf, g.scan_threads)
+            if got is None:  # the estimate was short, or an entry is not bytes
+                if not all(t.__class__ is bytes for t in entries):
+                    return None
+                buf = self._wire_text_buffer(eng, sum(map(len, entries)))
+                got = _gather_node_texts(entries, buf, g.scan_threads)
+                if got is None:
+                    return None
+            off = np.frombuffer(got[0], np.uint64)
+            esc = np.frombuffer(got[1], np.uint8)
+            entry = np.frombuffer(got[2], np.uint32)
+            n = len(esc)
+            g.node_wire_bytes_per_entry = max(g.node_wire_bytes_per_entry * 0.5, int(off[-1]) / n_e * 1.1)
+            if n == 0:  # (nothing but empty BATCHes)
+                return [[] for _ in range(n_e)]
+            t1 = _perf_counter()
+            cls, status, span = eng.wire_scan_node(np.frombuffer(buf, np.uint8), off, esc)
+            t2 = _perf_counter()
+            # the identifier spans are relative to the unwrapped text, which only the GPU holds
+            pinned = self._pinned(eng, "wire_uidx", 4 * n)
+            uidx, uniq_item = eng.wire_idents() if pinned is None else eng.wire_idents(pinned)
+            uniq = [str(b, "ascii") for b in eng.wire_ident_text(uniq_item)]
+            results, host, t3, t4 = self._wire_verdicts(eng, n, status, uidx, uidx.data, uniq, True)
+            none = cls == eng.NODE_NONE
+            host = [i for i in host if not none[i]]  # (no result for those, whatever their scan status)
+            g.stats["wire_items"] += n - int(np.count_nonzero(none)) - len(host)
+            counts = np.bincount(entry[~none], minlength=n_e)
+            if host:
+                self._node_wire_host(entries, buf, off, esc, entry, host, results, counts)
+                flat = []
+                for i in np.flatnonzero(~none).tolist():
+                    r = results[i]
+                    if r.__class__ is list:
+                        flat += r
+                    else:
+                        flat.append(r)
+            elif none.any():
+                flat = [results[i] for i in np.flatnonzero(~none).tolist()]
+            else:
+                flat = results
+            bounds = np.zeros(n_e + 1, np.int64)
+            np.cumsum(counts, out=bounds[1:])
+            bounds = bounds.tolist()
+            out = [flat[a:b] for a, b in zip(bounds, bounds[1:])]
+            t5 = _perf_counter()
+            g.last_wire_breakdown = {"gather": (t1 - t0) * 1e3, "scan": (t2 - t1) * 1e3, "keys": (t3 - t2) * 1e3,
+                                     "verify": (t4 - t3) * 1e3, "results": (t5 - t4) * 1e3,
+                                     "items": n, "host_items": len(host)}
+            return out
+
+    def _node_wire_host(self, entries, buf, off, esc, entry, host, results, counts):
+        """results[i] = the list of results of message i, for i in host, the host's
+        way: the entry itself, or the BATCH member turned back into its text and
+        visited one level down as in its BATCH; one authenticate_batch over all of
+        them.  counts[e] (results per entry) is adjusted to what they yield."""
+        import json
+        from .batching import requests_in_drain
+        text = memoryview(buf)
+        found = []
+        for i in host:
+            if esc[i]:
+                body = bytes(text[int(off[i]):int(off[i + 1])])
+                found.append(requests_in_drain([{"op": "BATCH", "messages": [json.loads(b'"' + body + b'"')]}]))
+            else:
+                found.append(requests_in_drain([entries[entry[i]]]))
+        flat = [r for reqs in found for r in reqs]
+        res = iter(self.authenticate_batch(flat) if flat else ())
+        for i, reqs in zip(host, found):
+            results[i] = [next(res) for _ in reqs]
+            counts[entry[i]] += len(reqs) - 1
+        self._g.stats["wire_host_items"] += len(host)
 
     def _authenticate_batch_each(self, msgs, identifiers=None, signatures=None):
         n = len(msgs)
@@ -2041,3 +2178,8 @@ class ReqAuthenticator:
         """The core authenticator's verdicts for a batch of request texts as they
         came off the wire (GpuAuthMixin.authenticate_wire_batch)."""
         return self.core_authenticator.authenticate_wire_batch(texts)
+
+    def authenticate_node_wire_batch(self, entries):
+        """The core authenticator's results, per entry, for a node stack's drain as
+        it came off the wire (GpuAuthMixin.authenticate_node_wire_batch)."""
+        return self.core_authenticator.authenticate_node_wire_batch(entries)

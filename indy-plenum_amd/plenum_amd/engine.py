@@ -336,7 +336,56 @@ class EdVerifyEngine:
         check(self._lib.edv_wire_scan(self._ctx, _ptr(text) if text.size else None, _ptr(text_off), n,
                                       _ptr(status) if n else None, _ptr(span) if n else None))
         self._wire_shape = (n, int(text_off[-1] - text_off[0]))
+        self._wire_span = span
         return status, span
+
+    supports_wire_node = True
+    NODE_REQUEST, NODE_HOST, NODE_NONE = 0, 1, 2  # edverify.h EDV_NODE_*
+
+    def wire_scan_node(self, text, text_off, esc):
+        """wire_scan for a node stack's messages (edv_wire_scan_node): message i =
+        text[text_off[i] : text_off[i + 1]], esc[i] = 1 where it is the still
+        escaped body of a BATCH member (_hostpack.gather_node_texts).  Returns
+        (cls uint8[n] -- NODE_REQUEST, NODE_HOST the caller decodes the
+        message, NODE_NONE it holds no signed request --, status, idr_span as
+        wire_scan; idr_span is relative to the unwrapped text in HBM, which
+        wire_ident_text reads).  The wire batch is left as wire_scan leaves it."""
+        text = text if isinstance(text, np.ndarray) and text.dtype == np.uint8 else np.frombuffer(text, np.uint8)
+        text_off = np.ascontiguousarray(text_off, dtype=np.uint64)
+        esc = np.ascontiguousarray(esc, dtype=np.uint8)
+        n = text_off.shape[0] - 1
+        if n < 0:
+            raise ValueError("text_off needs n + 1 entries")
+        if esc.shape[0] != n:
+            raise ValueError("shape mismatch: %d messages, %d escape flags" % (n, esc.shape[0]))
+        if int(text_off[-1]) > text.shape[0]:
+            raise ValueError("text_off exceeds the text buffer")
+        cls = np.ones(n, np.uint8)
+        status = np.ones(n, np.uint8)
+        span = np.zeros((n, 2), np.uint32)
+        check(self._lib.edv_wire_scan_node(self._ctx, _ptr(text) if text.size else None, _ptr(text_off),
+                                           _ptr(esc) if n else None, n, _ptr(cls) if n else None,
+                                           _ptr(status) if n else None, _ptr(span) if n else None))
+        self._wire_shape = (n, int(text_off[-1] - text_off[0]))
+        self._wire_span = span
+        return cls, status, span
+
+    def wire_ident_text(self, uniq_item):
+        """The identifiers (bytes each) of the wire batch's items uniq_item, read
+        out of the text the scan saw in HBM (edv_wire_ident_text): after
+        wire_scan_node the host does not hold that text."""
+        uniq_item = np.ascontiguousarray(uniq_item, dtype=np.uint32)
+        m = uniq_item.shape[0]
+        if m == 0:
+            return []
+        span = getattr(self, "_wire_span", None)
+        if span is None or (m and int(uniq_item.max()) >= span.shape[0]):
+            raise ValueError("no wire_scan_node batch holds these items")
+        out = np.zeros(int(span[uniq_item, 1].sum(dtype=np.uint64)), np.uint8)
+        off = np.zeros(m + 1, np.uint64)
+        check(self._lib.edv_wire_ident_text(self._ctx, _ptr(uniq_item), m, _ptr(out) if out.size else None, _ptr(off)))
+        raw = out.tobytes()
+        return [raw[a:b] for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
 
     def wire_verify(self, key_id, pk32=None):
         """Verdicts (bool[n]) of the wire batch's scanned items (edv_wire_verify):

@@ -12,9 +12,17 @@ resolution, verify, result list).
 found on the GPU (EDV_WIRE_IDENTS=1: edv_wire_idents, edv_wire_verify_idents) and on the host
 (EDV_WIRE_IDENTS=0: _hostpack.wire_idents); p50 and min-max of the `keys` phase and of the batch.
 
-usage: python tools/wire_probe.py [--n 1000000] [--signers 1000] [--batches 10] [--out FILE] [--idents-ab]
-       python tools/wire_probe.py --write-corpus FILE   (no GPU: the test corpus, length-prefixed,
-                                                         for indy-plenum_amd/build/wire_corpus_check)
+--node: a node stack's drain (nodeloop.drain_texts: per group of --members requests, one BATCH of
+their PROPAGATEs from each of the other pool - 1 nodes), about --n signed requests in all, for a
+4-node and a 25-node pool, three ways alternating in one process:
+  (a) authenticate_node_wire_batch(entries)                          split, unwrapped and scanned on the GPU
+  (b) authenticate_batch(batching.requests_in_drain(entries))        what a node pays today
+  (c) authenticate_wire_batch(the bare client texts, same requests)  the scan's own cost, no unwrap
+with the results asserted equal; p50 and min-max per path and per phase of (a) and (c).
+
+usage: python tools/wire_probe.py [--n 1000000] [--signers 1000] [--batches 10] [--out FILE] [--idents-ab | --node]
+       python tools/wire_probe.py --write-corpus FILE        (no GPU: the test corpora, length-prefixed,
+       python tools/wire_probe.py --write-node-corpus FILE    for indy-plenum_amd/build/wire_corpus_check [--node])
 """
 import argparse
 import json
@@ -37,6 +45,18 @@ def write_corpus(path):
             f.write(struct.pack("<I", len(t)))
             f.write(t)
     print("wrote %d texts to %s" % (len(texts), path))
+
+
+def write_node_corpus(path):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import wire_unwrap_model
+    corp = wire_unwrap_model.corpus()
+    entries = corp["clean"] + corp["mutated"]
+    with open(path, "wb") as f:
+        for t in entries:
+            f.write(struct.pack("<I", len(t)))
+            f.write(t)
+    print("wrote %d entries to %s" % (len(entries), path))
 
 
 def build(eng, n, signers, alias_len):
@@ -103,6 +123,68 @@ def idents_ab(eng, args, texts, idrs, vks):
     return out
 
 
+def _spread(ts):
+    return {"p50": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}
+
+
+def node_probe(eng, args, texts, dicts, idrs, vks):
+    """Paths (a), (b), (c) over a 4-node and a 25-node pool's drain of about args.n requests."""
+    from plenum_amd import nodeloop
+    from plenum_amd.batching import requests_in_drain
+    from plenum_amd.client_authn import GpuAuthNr
+    a = GpuAuthNr(engine=eng)
+    for idr, vk in zip(idrs, vks):
+        a.addIdr(idr, vk)
+    a.keys_settle()
+    phases = ("gather", "scan", "keys", "verify", "results")
+    out = {"n": args.n, "signers": args.signers, "batches": args.batches, "members": args.members, "pools": {}}
+    for pool in (4, 25):
+        reqs = min(len(dicts), max(1, args.n // (pool - 1)))
+        entries, bare = [], []
+        for g0 in range(0, reqs, args.members):
+            group = range(g0, min(reqs, g0 + args.members))
+            _, node = nodeloop.drain_texts([dicts[i] for i in group], n_nodes=pool)
+            entries += [t.encode() for t, _ in node]
+            bare += [texts[i] for i in group] * (pool - 1)
+        paths = {
+            "node_wire": lambda: a.authenticate_node_wire_batch(entries),
+            "loads_dicts": lambda: a.authenticate_batch(requests_in_drain(entries)),
+            "bare_wire": lambda: a.authenticate_wire_batch(bare),
+        }
+        for f in paths.values():  # warm-up: buffers grown, kernels loaded
+            f()
+        host0 = a.stats["wire_host_items"]
+        times = {k: [] for k in paths}
+        breakdown = {"node_wire": [], "bare_wire": []}
+        for _ in range(args.batches):
+            res = {}
+            for name, f in paths.items():
+                t0 = time.perf_counter()
+                res[name] = f()
+                times[name].append((time.perf_counter() - t0) * 1e3)
+                if name in breakdown:
+                    breakdown[name].append(dict(a._g.last_wire_breakdown))
+            flat = [r for per in res["node_wire"] for r in per]  # (per entry: flattened outside the timing)
+            assert flat == res["loads_dicts"] == res["bare_wire"], "results differ between the paths"
+            assert len(flat) == len(bare) and all(r.__class__ is str for r in flat)
+            del flat
+            del res
+        assert a.stats["wire_host_items"] == host0, "the GPU left messages to the host"
+        row = {"entries": len(entries), "requests": len(bare), "entry_bytes": sum(map(len, entries)),
+               "bare_bytes": sum(map(len, bare))}
+        for name, ts in times.items():
+            row[name] = {"batch_ms": _spread(ts)}
+            for k in phases if name in breakdown else ():
+                row[name][k + "_ms"] = _spread([b[k] for b in breakdown[name]])
+        p50 = {k: row[k]["batch_ms"]["p50"] for k in paths}
+        row["a_over_b"] = round(p50["node_wire"] / p50["loads_dicts"], 4)
+        row["a_minus_c_ms"] = round(p50["node_wire"] - p50["bare_wire"], 3)
+        out["pools"][str(pool)] = row
+        print("pool %d: %s" % (pool, json.dumps(row)), flush=True)
+        del entries, bare
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -111,20 +193,25 @@ def main():
     ap.add_argument("--batches", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--write-corpus", default=None)
+    ap.add_argument("--write-node-corpus", default=None)
     ap.add_argument("--idents-ab", action="store_true")
+    ap.add_argument("--node", action="store_true")
+    ap.add_argument("--members", type=int, default=70, help="--node: PROPAGATEs per BATCH")
     args = ap.parse_args()
     if args.write_corpus:
         return write_corpus(args.write_corpus)
+    if args.write_node_corpus:
+        return write_node_corpus(args.write_node_corpus)
     from plenum_amd import EdVerifyEngine
     from plenum_amd.client_authn import GpuAuthNr
     eng = EdVerifyEngine(0)
     t0 = time.perf_counter()
-    texts, dicts, idrs, vks = build(eng, args.n, args.signers, args.alias_len)
+    texts, dicts, idrs, vks = build(eng, args.n // 3 if args.node else args.n, args.signers, args.alias_len)
     print("built %d requests, %.0f B mean text, in %.1f s" % (
         args.n, sum(len(t) for t in texts[:1000]) / min(args.n, 1000), time.perf_counter() - t0), flush=True)
-    if args.idents_ab:
-        del dicts
-        line = json.dumps(idents_ab(eng, args, texts, idrs, vks))
+    if args.idents_ab or args.node:
+        line = json.dumps(node_probe(eng, args, texts, dicts, idrs, vks) if args.node
+                          else idents_ab(eng, args, texts, idrs, vks))
         print(line, flush=True)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
