@@ -399,6 +399,26 @@ int edv_wire_scan(edv_ctx *ctx, const uint8_t *text, const uint64_t *text_off, u
 #define EDV_NODE_NONE    2
 int edv_wire_scan_node(edv_ctx *ctx, const uint8_t *text, const uint64_t *text_off, const uint8_t *esc, uint64_t n,
                        uint8_t *cls, uint8_t *status, uint32_t *idr_span);
+/* edv_wire_scan_node with the BATCHes split on the GPU: entry e = text[entry_off[e] .. entry_off[e+1])
+ * is one rxMsgs entry, uploaded whole (pinned memory from edv_host_alloc is DMA'd in place).
+ * edv_node_split_count_kernel / _emit_kernel (csrc/node_split_lanes.h, DESIGN.md "Node messages")
+ * find each BATCH's member strings -- the same verdict and the same spans as csrc/node_split.h for
+ * every entry -- edv_node_copy_kernel puts the bodies back to back, and the unwrap and the scan
+ * run over them as for edv_wire_scan_node.  *n_msgs = m, the number of messages (an entry that is
+ * not split is one message, a split BATCH one per member), *n_bytes their bytes.  The results stay
+ * with the context for edv_wire_entries_result.  Leaves the wire batch exactly as edv_wire_scan_node
+ * does (m items, offsets from 0).  EDV_EINVAL: a null pointer, descending offsets, m >= EDV_WIRE_SKIP. */
+int edv_wire_scan_entries(edv_ctx *ctx, const uint8_t *text, const uint64_t *entry_off, uint64_t n_entries,
+                          uint64_t *n_msgs, uint64_t *n_bytes);
+/* The results of the last edv_wire_scan_entries: cls[m], status[m], idr_span[2m] as edv_wire_scan_node
+ * returns them; esc[m] (1: the still-escaped body of a BATCH member), entry[m] (ascending: the entry
+ * the message came from), at[m] (the position of the message's first byte in the caller's text),
+ * off[m+1] (message i's bytes are off[i+1] - off[i]; from 0).  EDV_EINVAL when the wire batch did
+ * not come from edv_wire_scan_entries. */
+int edv_wire_entries_result(edv_ctx *ctx, uint8_t *cls, uint8_t *status, uint32_t *idr_span, uint8_t *esc,
+                            uint32_t *entry, uint64_t *at, uint64_t *off);
+/* DIAGNOSTIC: the message bodies edv_wire_scan_entries put back to back, off[m] bytes. */
+int edv_wire_raw_readback(edv_ctx *ctx, uint8_t *raw);
 /* The identifier bytes of the wire batch's items uniq_item[0 .. n_uniq) (status 0 each; what
  * edv_wire_idents returned), gathered on the GPU from the text the scan read: identifier j at
  * out[out_off[j] .. out_off[j+1]), out_off[n_uniq+1] written here from 0.  out needs room for

@@ -20,6 +20,9 @@
 //                          identifier spans and signing bytes in HBM (wire_scan.h)
 //   edv_wire_unwrap_kernel   node messages (PROPAGATEs, BATCH members) -> texts the scan
 //                          accepts, in front of it (wire_unwrap.h)
+//   edv_node_split_count_kernel / _emit_kernel / edv_node_copy_kernel   rxMsgs entries ->
+//                          their messages (a BATCH's member strings cut out, any other entry
+//                          whole), in front of the unwrap (node_split_lanes.h)
 //   edv_wire_ident_insert_kernel / _flag_kernel / _number_kernel   the wire batch's
 //                          distinct identifiers in first-occurrence order and each
 //                          item's index into them (wire_idents.h);
@@ -52,6 +55,7 @@
 #include "fe_lanes.h"
 #include "sha256.h"
 #include "verify_core.h"
+#include "node_split_lanes.h"
 #include "wire_idents.h"
 #include "wire_scan.h"
 #include "wire_unwrap.h"
@@ -801,6 +805,184 @@ __global__ __launch_bounds__(kWireThreads) void edv_wire_unwrap_kernel(
     __syncthreads();  // every lane has read s_next / s_lo / s_hi and s_out before the next tile resets them
     t0 = next & ~15ull;
   }
+}
+
+// ---- the BATCH split in front of the unwrap (edverify.h edv_wire_scan_entries; the lane code is
+// node_split_lanes.h, the definition node_split.h).  The rxMsgs entries lie whole in HBM (byte b of
+// the caller's buffer at ent[b - base + kWirePad], kWireTail bytes behind).  One wave per entry,
+// kSplitWaves entries per workgroup, no LDS and no barrier: lane l takes the 16 bytes at
+// q + 16 l of each 1,024-byte step q (steps start at the 16-byte boundary at or before the entry:
+// one aligned 16-byte load per lane, the neighbours' bytes masked off), the wave composes the
+// lanes' state maps by shuffles and carries the state to the next step.  The head and the tail
+// are walked by lane 0.
+//   count (pass A)  verdict[e] (1 split), cnt[e] messages, bytes[e] body bytes; an entry that is
+//                   not split is one message of its own length
+//   emit (pass B)   after the exclusive sums msg0 / body0 over the entries: per message its
+//                   offset among the bodies, escape flag, entry and position in the caller's buffer
+//   copy            message i's bytes from the entries to raw[kWirePad + off[i] ..): one wave per
+//                   message, aligned 16-byte stores
+constexpr uint32_t kSplitWaves = 4;
+
+__device__ __forceinline__ NslBytes nsl_load_aligned(const uint8_t* __restrict__ ent, uint64_t q0, uint64_t ea,
+                                                     uint64_t eb) {
+  NslBytes x;
+  nsl_bounds(q0, ea, eb, x.lo, x.hi);
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (x.lo < x.hi) v = *(const uint4*)(ent + kWirePad + q0);  // (q0 < eb: inside the tail at the latest)
+  x.w[0] = v.x;
+  x.w[1] = v.y;
+  x.w[2] = v.z;
+  x.w[3] = v.w;
+  return x;
+}
+
+// inclusive scan of the lanes' maps, lane 0's first
+__device__ __forceinline__ uint32_t nsl_wave_maps(uint32_t m, uint32_t lane) {
+#pragma unroll
+  for (uint32_t d = 1; d < kNslLanes; d <<= 1) {
+    const uint32_t o = (uint32_t)__shfl_up((int)m, d, kNslLanes);
+    if (lane >= d) m = nsl_compose(o, m);
+  }
+  return m;
+}
+__device__ __forceinline__ uint64_t nsl_shfl(uint64_t v, uint32_t src) {
+  return (uint64_t)__shfl((unsigned long long)v, (int)src, kNslLanes);
+}
+__device__ __forceinline__ uint64_t nsl_wave_sums(uint64_t v, uint32_t lane) {  // inclusive
+#pragma unroll
+  for (uint32_t d = 1; d < kNslLanes; d <<= 1) {
+    const uint64_t o = (uint64_t)__shfl_up((unsigned long long)v, d, kNslLanes);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+// One step: the lane's state on entry from carry (uniform), the state after the step into carry.
+__device__ __forceinline__ uint32_t nsl_wave_state(const NslBytes& x, uint64_t q0, uint64_t arr, uint32_t lane,
+                                                   uint32_t& carry, bool& bad) {
+  const uint32_t incl = nsl_wave_maps(nsl_lane_map(x, q0, arr, bad), lane);
+  const uint32_t before = (uint32_t)__shfl_up((int)incl, 1, kNslLanes);
+  const uint32_t state = nsl_apply(lane ? before : kNslIdentity, carry);
+  carry = nsl_apply((uint32_t)__shfl((int)incl, kNslLanes - 1, kNslLanes), carry);
+  return state;
+}
+
+__global__ __launch_bounds__(kSplitWaves * kNslLanes) void edv_node_split_count_kernel(
+    const uint8_t* __restrict__ ent, const uint64_t* __restrict__ eoff, uint64_t base, uint64_t e0, uint64_t e1,
+    uint8_t* __restrict__ verdict, uint64_t* __restrict__ cnt, uint64_t* __restrict__ bytes) {
+  const uint32_t lane = threadIdx.x % kNslLanes;
+  const uint64_t e = e0 + (uint64_t)blockIdx.x * kSplitWaves + threadIdx.x / kNslLanes;
+  if (e >= e1) return;  // (the whole wave)
+  const uint64_t ea = eoff[e] - base, eb = eoff[e + 1] - base, n = eb - ea;
+  const uint8_t* t = ent + kWirePad + ea;
+  uint64_t arr = kNslFail;
+  if (lane == 0) arr = nsl_head(t, n);
+  arr = nsl_shfl(arr, 0);
+  bool split = false;
+  uint64_t members = 0, body = 0;
+  if (arr != kNslFail) {
+    arr += ea;
+    NslRun run{kNslStart, 0, 0, kNslFail};
+    uint32_t carry = kNslStart;
+    bool bad = false;
+    for (uint64_t q = ea & ~15ull; q < eb; q += kNslStep) {
+      const uint64_t q0 = q + (uint64_t)kNslLaneBytes * lane;
+      const NslBytes x = nsl_load_aligned(ent, q0, ea, eb);
+      run.state = nsl_wave_state(x, q0, arr, lane, carry, bad);
+      nsl_lane_replay(x, q0, arr, run, NslNoEmit{});
+    }
+    members = nsl_shfl(nsl_wave_sums(run.members, lane), kNslLanes - 1);
+    body = nsl_shfl(nsl_wave_sums(run.delta, lane), kNslLanes - 1);
+    // (one lane at most met the ']': DONE absorbs)
+    const uint64_t met = __ballot(run.close != kNslFail);
+    if (!__any(bad) && carry == kNslDone && met) {
+      const uint64_t close = nsl_shfl(run.close, (uint32_t)__ffsll((unsigned long long)met) - 1);
+      int ok = 0;
+      if (lane == 0) ok = nsl_tail(t, close - ea + 1, n) ? 1 : 0;
+      split = __shfl(ok, 0, kNslLanes) != 0;
+    }
+  }
+  if (lane == 0) {
+    verdict[e] = split ? 1 : 0;
+    cnt[e] = split ? members : 1;
+    bytes[e] = split ? body : n;
+  }
+}
+
+__global__ __launch_bounds__(kSplitWaves * kNslLanes) void edv_node_split_emit_kernel(
+    const uint8_t* __restrict__ ent, const uint64_t* __restrict__ eoff, uint64_t base, uint64_t n_e,
+    const uint8_t* __restrict__ verdict, const uint64_t* __restrict__ msg0, const uint64_t* __restrict__ body0,
+    uint64_t m, uint64_t* __restrict__ off, uint8_t* __restrict__ esc, uint32_t* __restrict__ entry,
+    uint64_t* __restrict__ at) {
+  const uint32_t lane = threadIdx.x % kNslLanes;
+  const uint64_t e = (uint64_t)blockIdx.x * kSplitWaves + threadIdx.x / kNslLanes;
+  if (e >= n_e) return;  // (the whole wave)
+  const uint64_t ea = eoff[e] - base, eb = eoff[e + 1] - base;
+  const uint64_t k0 = msg0[e], k1 = msg0[e + 1] < m ? msg0[e + 1] : m, b0 = body0[e];
+  if (e == n_e - 1 && lane == 0) off[m] = body0[n_e];
+  if (!verdict[e]) {
+    if (lane == 0 && k0 < k1) {
+      off[k0] = b0;
+      esc[k0] = 0;
+      entry[k0] = (uint32_t)e;
+      at[k0] = base + ea;
+    }
+    return;
+  }
+  uint64_t arr = kNslFail;
+  if (lane == 0) arr = nsl_head(ent + kWirePad + ea, eb - ea);
+  arr = nsl_shfl(arr, 0);
+  if (arr == kNslFail) return;  // (never: the count pass split it)
+  arr += ea;
+  // a message index outside the entry's own [k0, k1) is never written (never met: the two passes
+  // run the same lane code over the same bytes)
+  const auto emit = [=](uint64_t index, uint64_t body, uint64_t first) {
+    const uint64_t k = k0 + index;
+    if (k < k1) {
+      off[k] = b0 + body;
+      esc[k] = 1;
+      entry[k] = (uint32_t)e;
+      at[k] = base + first;
+    }
+  };
+  uint32_t carry = kNslStart;
+  uint64_t carry_members = 0, carry_delta = 0;
+  bool bad = false;
+  for (uint64_t q = ea & ~15ull; q < eb && carry != kNslDone && carry != kNslErr; q += kNslStep) {
+    const uint64_t q0 = q + (uint64_t)kNslLaneBytes * lane;
+    const NslBytes x = nsl_load_aligned(ent, q0, ea, eb);
+    const uint32_t state = nsl_wave_state(x, q0, arr, lane, carry, bad);
+    NslRun tally{state, 0, 0, kNslFail};
+    nsl_lane_replay(x, q0, arr, tally, NslNoEmit{});
+    const uint64_t mem = nsl_wave_sums(tally.members, lane), del = nsl_wave_sums(tally.delta, lane);
+    NslRun run{state, carry_members + mem - tally.members, carry_delta + del - tally.delta, kNslFail};
+    nsl_lane_replay(x, q0, arr, run, emit);
+    carry_members += nsl_shfl(mem, kNslLanes - 1);
+    carry_delta += nsl_shfl(del, kNslLanes - 1);
+  }
+}
+
+__global__ __launch_bounds__(kSplitWaves * kNslLanes) void edv_node_copy_kernel(
+    const uint8_t* __restrict__ ent, uint64_t base, uint64_t total, const uint64_t* __restrict__ off,
+    const uint64_t* __restrict__ at, uint64_t m, uint64_t raw_bytes, uint8_t* __restrict__ raw) {
+  const uint32_t lane = threadIdx.x % kNslLanes;
+  const uint64_t i = (uint64_t)blockIdx.x * kSplitWaves + threadIdx.x / kNslLanes;
+  if (i >= m) return;
+  const uint64_t a = off[i], b = off[i + 1], from = at[i] - base;
+  if (b < a || b > raw_bytes || at[i] < base || from > total || b - a > total - from) return;  // (never)
+  const uint64_t len = b - a;
+  const uint8_t* src = ent + kWirePad + from;
+  uint8_t* dst = raw + kWirePad + a;
+  uint64_t head = (16 - ((kWirePad + a) & 15)) & 15;  // (raw itself is 16-byte aligned)
+  if (head > len) head = len;
+  if (lane < head) dst[lane] = src[lane];
+  const uint64_t chunks = (len - head) / 16;
+  for (uint64_t c = lane; c < chunks; c += kNslLanes) {
+    uint4 v;
+    __builtin_memcpy(&v, src + head + 16 * c, 16);
+    *(uint4*)(dst + head + 16 * c) = v;
+  }
+  const uint64_t done = head + 16 * chunks;
+  if (done + lane < len) dst[done + lane] = src[done + lane];
 }
 
 // The identifier bytes of the items item[0 .. m) of the wire batch, back to back: identifier j at
@@ -1740,6 +1922,12 @@ struct edv_ctx {
   Buf w_raw, w_esc, w_cls, wh_esc, w_itext_in, w_itext, wh_itext;
   uint64_t wire_n = 0, wire_bytes = 0, wire_base = 0;
   bool wire_ok = false;
+  // edv_wire_scan_entries: the uploaded entries and their offsets; per entry the split's verdict,
+  // message count and body bytes and the exclusive sums of those ([n_e + 1] each), the sums'
+  // scratch; per message its entry and its position in the caller's buffer; pinned staging for
+  // the two totals and for what edv_wire_entries_result hands out
+  Buf w_ent, w_eoff, w_everd, w_ecnt, w_ebytes, w_emsg0, w_ebody0, w_etmp, w_mentry, w_mat, wh_etot, wh_eres;
+  bool wire_entries_ok = false;  // the wire batch came from edv_wire_scan_entries
   // edv_wire_idents: the table (owner [cap] then first [cap]), per item its slot, flag, rank
   // ([n + 1] each) and index (w_uidx, kept for edv_wire_verify_idents until the next scan), the
   // first occurrences, the scan's scratch, a flag word, the per-identifier key ids; pinned staging
@@ -3268,6 +3456,7 @@ static int wire_scan_run(edv_ctx* ctx, bool node, const uint8_t* text, const uin
   if (r) return r;
   ctx->wire_ok = false;
   ctx->wire_uidx_ok = false;
+  ctx->wire_entries_ok = false;
   if (!text_off || (n && (!status || !idr_span))) return set_err(EDV_EINVAL, "null pointer");
   if (node && n && (!esc || !cls)) return set_err(EDV_EINVAL, "null pointer");
   if (n >= EDV_WIRE_SKIP) return set_err(EDV_EINVAL, "too many items");
@@ -3374,6 +3563,205 @@ int edv_wire_scan(edv_ctx* ctx, const uint8_t* text, const uint64_t* text_off, u
 int edv_wire_scan_node(edv_ctx* ctx, const uint8_t* text, const uint64_t* text_off, const uint8_t* esc, uint64_t n,
                        uint8_t* cls, uint8_t* status, uint32_t* idr_span) {
   return wire_scan_run(ctx, true, text, text_off, esc, n, cls, status, idr_span);
+}
+
+// ---- rxMsgs entries from the wire, the BATCHes split on the GPU
+// bytes of entries per upload + count launch
+constexpr uint64_t kEntChunkBytes = 32ull << 20;
+
+static int wire_event(edv_ctx* ctx, size_t k, hipEvent_t* ev) {
+  while (ctx->wire_ev.size() <= k) {
+    hipEvent_t e;
+    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    ctx->wire_ev.push_back(e);
+  }
+  *ev = ctx->wire_ev[k];
+  return 0;
+}
+
+int edv_wire_scan_entries(edv_ctx* ctx, const uint8_t* text, const uint64_t* entry_off, uint64_t n_e, uint64_t* n_msgs,
+                          uint64_t* n_bytes) {
+  int r = set_device(ctx);
+  if (r) return r;
+  ctx->wire_ok = false;
+  ctx->wire_uidx_ok = false;
+  ctx->wire_entries_ok = false;
+  if (!entry_off || !n_msgs || !n_bytes) return set_err(EDV_EINVAL, "null pointer");
+  if (n_e >= EDV_WIRE_SKIP) return set_err(EDV_EINVAL, "too many entries");
+  uint64_t bad = 0;
+  for (uint64_t e = 0; e < n_e; ++e) bad |= (uint64_t)(entry_off[e] > entry_off[e + 1]);
+  if (bad) return set_err(EDV_EINVAL, "entry offsets not ascending");
+  const uint64_t base = entry_off[0], total = entry_off[n_e] - base;
+  if (total && !text) return set_err(EDV_EINVAL, "null text");
+  const auto empty = [&] {
+    ctx->wire_n = ctx->wire_bytes = ctx->wire_base = 0;
+    ctx->wire_status.clear();
+    ctx->wire_ok = ctx->wire_entries_ok = true;
+    *n_msgs = *n_bytes = 0;
+    return 0;
+  };
+  if (n_e == 0) return empty();
+  hipStream_t st = ctx->stream, cs = ctx->stream_copy;
+  size_t tmp = 0;
+  HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)(n_e + 1),
+                                  rocprim::plus<uint64_t>(), st));
+  if ((r = ensure(ctx->w_ent, kWirePad + total + kWireTail)) || (r = ensure(ctx->w_eoff, 8 * (n_e + 1))) ||
+      (r = ensure(ctx->w_everd, n_e)) || (r = ensure(ctx->w_ecnt, 8 * (n_e + 1))) ||
+      (r = ensure(ctx->w_ebytes, 8 * (n_e + 1))) || (r = ensure(ctx->w_emsg0, 8 * (n_e + 1))) ||
+      (r = ensure(ctx->w_ebody0, 8 * (n_e + 1))) || (r = ensure(ctx->w_etmp, tmp)) ||
+      (r = ensure_pinned(ctx->wh_etot, 16)))
+    return r;
+  const void* src_text = text + base;
+  if (total && !pinned_range(src_text, total)) {
+    if ((r = ensure_pinned(ctx->wh_text, total))) return r;
+    stage_copy(ctx->wh_text.p, src_text, total);
+    src_text = ctx->wh_text.p;
+  }
+  const void* src_off = entry_off;
+  if (!pinned_range(entry_off, 8 * (n_e + 1))) {
+    if ((r = ensure_pinned(ctx->wh_off, 8 * (n_e + 1)))) return r;
+    stage_copy(ctx->wh_off.p, entry_off, 8 * (n_e + 1));
+    src_off = ctx->wh_off.p;
+  }
+  // pass A: chunk c's entries go up on stream_copy while chunk c - 1 is counted on the context
+  // stream (a lane's 16-byte load may touch the first bytes of the next chunk before they arrive:
+  // bytes of another entry, masked off)
+  hipEvent_t ev;
+  if ((r = wire_event(ctx, 0, &ev))) return r;
+  HIP_TRY(hipEventRecord(ev, st));  // (the copies start after the work already queued)
+  HIP_TRY(hipStreamWaitEvent(cs, ev, 0));
+  uint8_t* d_ent = (uint8_t*)ctx->w_ent.p;
+  uint64_t* d_eoff = (uint64_t*)ctx->w_eoff.p;
+  uint64_t *d_cnt = (uint64_t*)ctx->w_ecnt.p, *d_bytes = (uint64_t*)ctx->w_ebytes.p;
+  uint64_t *d_msg0 = (uint64_t*)ctx->w_emsg0.p, *d_body0 = (uint64_t*)ctx->w_ebody0.p;
+  HIP_TRY(hipMemsetAsync(d_ent, 0, kWirePad, cs));
+  HIP_TRY(hipMemsetAsync(d_ent + kWirePad + total, 0, kWireTail, cs));
+  HIP_TRY(hipMemsetAsync(d_cnt + n_e, 0, 8, cs));  // (the sums' last element: the totals)
+  HIP_TRY(hipMemsetAsync(d_bytes + n_e, 0, 8, cs));
+  HIP_TRY(hipMemcpyAsync(d_eoff, src_off, 8 * (n_e + 1), hipMemcpyHostToDevice, cs));
+  size_t c = 1;
+  for (uint64_t e0 = 0; e0 < n_e; ++c) {
+    uint64_t e1 = (uint64_t)(std::upper_bound(entry_off + e0 + 1, entry_off + n_e + 1, entry_off[e0] + kEntChunkBytes) -
+                             entry_off) - 1;
+    if (e1 <= e0) e1 = e0 + 1;  // (one entry over the bound: a chunk of its own)
+    const uint64_t ta = entry_off[e0] - base, tb = entry_off[e1] - base;
+    if (tb > ta)
+      HIP_TRY(hipMemcpyAsync(d_ent + kWirePad + ta, (const uint8_t*)src_text + ta, tb - ta, hipMemcpyHostToDevice, cs));
+    if ((r = wire_event(ctx, c, &ev))) return r;
+    HIP_TRY(hipEventRecord(ev, cs));
+    HIP_TRY(hipStreamWaitEvent(st, ev, 0));
+    hipLaunchKernelGGL(edv_node_split_count_kernel, dim3((uint32_t)div_up(e1 - e0, kSplitWaves)),
+                       dim3(kSplitWaves * kNslLanes), 0, st, (const uint8_t*)d_ent, (const uint64_t*)d_eoff, base, e0,
+                       e1, (uint8_t*)ctx->w_everd.p, d_cnt, d_bytes);
+    HIP_TRY(hipGetLastError());
+    e0 = e1;
+  }
+  // each entry's first message and first body byte; the totals size everything behind: the one
+  // synchronisation of the split
+  HIP_TRY(rocprim::exclusive_scan(ctx->w_etmp.p, tmp, d_cnt, d_msg0, (uint64_t)0, (size_t)(n_e + 1),
+                                  rocprim::plus<uint64_t>(), st));
+  HIP_TRY(rocprim::exclusive_scan(ctx->w_etmp.p, tmp, d_bytes, d_body0, (uint64_t)0, (size_t)(n_e + 1),
+                                  rocprim::plus<uint64_t>(), st));
+  uint64_t* tot = (uint64_t*)ctx->wh_etot.p;
+  HIP_TRY(hipMemcpyAsync(tot, d_msg0 + n_e, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(tot + 1, d_body0 + n_e, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint64_t m = tot[0], bodies = tot[1];
+  if (m >= EDV_WIRE_SKIP) return set_err(EDV_EINVAL, "too many items");
+  if (bodies > total) return set_err(EDV_EHIP, "the split's bodies exceed the entries");
+  if (m == 0) return empty();  // (nothing but empty BATCHes)
+  ctx->wire_n = m;
+  ctx->wire_bytes = bodies;
+  ctx->wire_base = 0;
+  ctx->wire_status.assign((size_t)m, (uint8_t)EDV_WIRE_HOST);
+  const uint64_t bytes = kWirePad + bodies + kWireTail;
+  if ((r = ensure(ctx->w_text, bytes)) || (r = ensure(ctx->w_msg, bytes)) || (r = ensure(ctx->w_sig, 64 * m)) ||
+      (r = ensure(ctx->w_spans, 16 * m)) || (r = ensure(ctx->w_status, m)) || (r = ensure(ctx->w_idr, 8 * m)) ||
+      (r = ensure(ctx->w_off, 8 * (m + 1))) || (r = ensure_pinned(ctx->wh_out, 10 * m)) ||
+      (r = ensure(ctx->w_raw, bytes)) || (r = ensure(ctx->w_esc, m)) || (r = ensure(ctx->w_cls, m)) ||
+      (r = ensure(ctx->w_mentry, 4 * m)) || (r = ensure(ctx->w_mat, 8 * m)) ||
+      (r = ensure_pinned(ctx->wh_eres, 21 * m + 8)))
+    return r;
+  uint8_t *d_text = (uint8_t*)ctx->w_text.p, *d_raw = (uint8_t*)ctx->w_raw.p;
+  uint64_t* d_off = (uint64_t*)ctx->w_off.p;
+  HIP_TRY(hipMemsetAsync(d_text, 0, kWirePad, st));
+  HIP_TRY(hipMemsetAsync(d_text + kWirePad + bodies, 0, kWireTail, st));
+  HIP_TRY(hipMemsetAsync(d_raw, 0, kWirePad, st));
+  HIP_TRY(hipMemsetAsync(d_raw + kWirePad + bodies, 0, kWireTail, st));
+  // pass B and the bodies: what wire_scan_run uploads for edv_wire_scan_node, base 0
+  hipLaunchKernelGGL(edv_node_split_emit_kernel, dim3((uint32_t)div_up(n_e, kSplitWaves)),
+                     dim3(kSplitWaves * kNslLanes), 0, st, (const uint8_t*)d_ent, (const uint64_t*)d_eoff, base, n_e,
+                     (const uint8_t*)ctx->w_everd.p, (const uint64_t*)d_msg0, (const uint64_t*)d_body0, m, d_off,
+                     (uint8_t*)ctx->w_esc.p, (uint32_t*)ctx->w_mentry.p, (uint64_t*)ctx->w_mat.p);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(edv_node_copy_kernel, dim3((uint32_t)div_up(m, kSplitWaves)), dim3(kSplitWaves * kNslLanes), 0,
+                     st, (const uint8_t*)d_ent, base, total, (const uint64_t*)d_off, (const uint64_t*)ctx->w_mat.p, m,
+                     bodies, d_raw);
+  HIP_TRY(hipGetLastError());
+  for (uint64_t c0 = 0; c0 < m; c0 += kWireChunk) {
+    const uint64_t cn = m - c0 < kWireChunk ? m - c0 : kWireChunk;
+    hipLaunchKernelGGL(edv_wire_unwrap_kernel, dim3((uint32_t)div_up(cn, kWireThreads)), dim3(kWireThreads), 0, st,
+                       (const uint8_t*)d_raw, (const uint64_t*)d_off, (const uint8_t*)ctx->w_esc.p, (uint64_t)0, c0,
+                       c0 + cn, d_text, (uint8_t*)ctx->w_cls.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(edv_wire_scan_kernel, dim3((uint32_t)div_up(cn, kWireThreads)), dim3(kWireThreads), 0, st,
+                       (const uint8_t*)d_text, (const uint64_t*)d_off, (uint64_t)0, c0, c0 + cn, m,
+                       (uint8_t*)ctx->w_msg.p, (uint8_t*)ctx->w_sig.p, (uint8_t*)ctx->w_status.p,
+                       (uint32_t*)ctx->w_idr.p, (uint64_t*)ctx->w_spans.p);
+    HIP_TRY(hipGetLastError());
+  }
+  uint8_t* h = (uint8_t*)ctx->wh_out.p;  // identifier spans, the status bytes, the classes
+  HIP_TRY(hipMemcpyAsync(h, ctx->w_idr.p, 8 * m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h + 8 * m, ctx->w_status.p, m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h + 9 * m, ctx->w_cls.p, m, hipMemcpyDeviceToHost, st));
+  uint8_t* g = (uint8_t*)ctx->wh_eres.p;  // off [m + 1], at [m], entry [m], esc [m]
+  HIP_TRY(hipMemcpyAsync(g, d_off, 8 * (m + 1), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(g + 8 * (m + 1), ctx->w_mat.p, 8 * m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(g + 16 * m + 8, ctx->w_mentry.p, 4 * m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(g + 20 * m + 8, ctx->w_esc.p, m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  memcpy(ctx->wire_status.data(), h + 8 * m, m);
+  *n_msgs = m;
+  *n_bytes = bodies;
+  ctx->wire_ok = ctx->wire_entries_ok = true;
+  return 0;
+}
+
+int edv_wire_entries_result(edv_ctx* ctx, uint8_t* cls, uint8_t* status, uint32_t* idr_span, uint8_t* esc,
+                            uint32_t* entry, uint64_t* at, uint64_t* off) {
+  if (!ctx) return set_err(EDV_EINVAL, "null context");
+  if (!ctx->wire_ok || !ctx->wire_entries_ok)
+    return set_err(EDV_EINVAL, "no wire batch of entries (edv_wire_scan_entries first)");
+  if (!off) return set_err(EDV_EINVAL, "null pointer");
+  const uint64_t m = ctx->wire_n;
+  if (m == 0) {
+    off[0] = 0;
+    return 0;
+  }
+  if (!cls || !status || !idr_span || !esc || !entry || !at) return set_err(EDV_EINVAL, "null pointer");
+  const uint8_t *h = (const uint8_t*)ctx->wh_out.p, *g = (const uint8_t*)ctx->wh_eres.p;
+  memcpy(idr_span, h, 8 * m);
+  memcpy(status, h + 8 * m, m);
+  memcpy(cls, h + 9 * m, m);
+  memcpy(off, g, 8 * (m + 1));
+  memcpy(at, g + 8 * (m + 1), 8 * m);
+  memcpy(entry, g + 16 * m + 8, 4 * m);
+  memcpy(esc, g + 20 * m + 8, m);
+  return 0;
+}
+
+int edv_wire_raw_readback(edv_ctx* ctx, uint8_t* raw) {
+  int r = set_device(ctx);
+  if (r) return r;
+  if (!ctx->wire_ok || !ctx->wire_entries_ok)
+    return set_err(EDV_EINVAL, "no wire batch of entries (edv_wire_scan_entries first)");
+  const uint64_t total = ctx->wire_bytes;
+  if (total == 0) return 0;
+  if (!raw) return set_err(EDV_EINVAL, "null pointer");
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemcpyAsync(raw, (const uint8_t*)ctx->w_raw.p + kWirePad, total, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return 0;
 }
 
 // The items idx[0 .. m) of the wire batch (status 0) on one path: their signatures and spans
@@ -3867,7 +4255,9 @@ void edv_destroy(edv_ctx* ctx) {
                           &ctx->wh_out, &ctx->wh_keys, &ctx->wh_bits, &ctx->w_itab, &ctx->w_islot, &ctx->w_iflag,
                           &ctx->w_irank, &ctx->w_uidx, &ctx->w_uitem, &ctx->w_itmp, &ctx->w_ibad, &ctx->w_ikid,
                           &ctx->wh_idents, &ctx->wh_ikid, &ctx->w_raw, &ctx->w_esc, &ctx->w_cls, &ctx->wh_esc,
-                          &ctx->w_itext_in, &ctx->w_itext, &ctx->wh_itext})
+                          &ctx->w_itext_in, &ctx->w_itext, &ctx->wh_itext, &ctx->w_ent, &ctx->w_eoff, &ctx->w_everd,
+                          &ctx->w_ecnt, &ctx->w_ebytes, &ctx->w_emsg0, &ctx->w_ebody0, &ctx->w_etmp, &ctx->w_mentry,
+                          &ctx->w_mat, &ctx->wh_etot, &ctx->wh_eres})
     free_buf(*b);
   for (int k = 0; k < edv_ctx::kSets; ++k) {
     for (edv_ctx::Buf* b : {&ctx->d_stage_set[k], &ctx->d_spans[k], &ctx->s_sig[k], &ctx->s_key[k], &ctx->s_bits[k],

@@ -729,6 +729,70 @@ int64_t hc_wire_idents(const uint8_t* text, const uint64_t* off_p, uint64_t n, c
 }
 }  // extern "C"
 
+// ---- the device BATCH split (node_split_lanes.h, the code of edv_node_split_count_kernel's and
+// edv_node_split_emit_kernel's lanes) on the CPU as an emulated wave: 64 lanes one after the other,
+// the same Hillis-Steele composition the shuffles do and the same carry from step to step; every
+// read asserted inside the entry, every write inside the outputs.  For tests/test_node_split_lanes.py
+// and the node wire double.
+#include "node_split_wave_host.h"
+namespace {
+struct CheckedEntry {
+  const uint8_t* p;
+  uint64_t n;
+  uint8_t operator[](uint64_t i) const {
+    EDV_ASSERT(i < n);
+    return p[i];
+  }
+};
+
+}  // namespace
+extern "C" {
+// The messages of n_e entries (entry e = text[entry_off[e] .. entry_off[e + 1])) as the two device
+// passes make them.  Returns m, the number of messages, and their bytes in *n_bytes.  With off null
+// that is all (pass A and the sums); otherwise cap >= m and off[m + 1] (from 0), esc[m], entry[m],
+// at[m] (the position of the message's first byte in text) are written (pass B).
+int64_t hc_node_split_lanes(const uint8_t* text, const uint64_t* entry_off, uint64_t n_e, uint64_t cap, uint64_t* off_p,
+                            uint8_t* esc_p, uint32_t* entry_p, uint64_t* at_p, uint64_t* n_bytes) {
+  const uint64_t base = n_e ? entry_off[0] : 0;
+  std::vector<EntryCount> count((size_t)n_e);
+  std::vector<uint64_t> msg0((size_t)n_e + 1, 0), body0((size_t)n_e + 1, 0);
+  for (uint64_t e = 0; e < n_e; ++e) {
+    EDV_ASSERT(entry_off[e] <= entry_off[e + 1]);
+    const CheckedEntry t{text + entry_off[e], entry_off[e + 1] - entry_off[e]};
+    count[e] = lanes_count(t, entry_off[e] - base, entry_off[e + 1] - base);
+    msg0[e + 1] = msg0[e] + count[e].members;
+    body0[e + 1] = body0[e] + count[e].bytes;
+  }
+  const uint64_t m = msg0[n_e];
+  *n_bytes = body0[n_e];
+  if (!off_p) return (int64_t)m;
+  EDV_ASSERT(cap >= m);
+  const CheckedArr<uint64_t> off{off_p, m + 1}, at{at_p, m};
+  const CheckedArr<uint8_t> esc{esc_p, m};
+  const CheckedArr<uint32_t> entry{entry_p, m};
+  off[m] = body0[n_e];
+  for (uint64_t e = 0; e < n_e; ++e) {
+    const uint64_t k0 = msg0[e], k1 = msg0[e + 1], b0 = body0[e];
+    if (!count[e].split) {
+      off[k0] = b0;
+      esc[k0] = 0;
+      entry[k0] = (uint32_t)e;
+      at[k0] = entry_off[e];
+      continue;
+    }
+    const CheckedEntry t{text + entry_off[e], entry_off[e + 1] - entry_off[e]};
+    lanes_emit(t, entry_off[e] - base, entry_off[e + 1] - base, [&](uint64_t index, uint64_t body, uint64_t first) {
+      EDV_ASSERT(k0 + index < k1);
+      off[k0 + index] = b0 + body;
+      esc[k0 + index] = 1;
+      entry[k0 + index] = (uint32_t)e;
+      at[k0 + index] = base + first;
+    });
+  }
+  return (int64_t)m;
+}
+}  // extern "C"
+
 // ---- the CPU twins of tests/native/ed_probe.hip's one-item-per-lane entry points (same
 // signatures, the same calls: csrc/ed_probe_ops.h), for tests/test_ed_edges.py: the tables of
 // tests/ed_edge_common.py through this build's EDV_BOUND_CHECK assertions.

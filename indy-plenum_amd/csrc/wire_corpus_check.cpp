@@ -11,7 +11,11 @@
 // its length, goes through the BATCH parse (node_split.h); every message that yields -- a member
 // body, or the entry whole -- is copied into a block of exactly its length and unwrapped
 // (wire_unwrap.h, the lane code of edv_wire_unwrap_kernel) into another, and the result is
-// scanned.  Every entry is also unwrapped whole both as plain text and as an escaped body.
+// scanned.  Every entry is also unwrapped whole both as plain text and as an escaped body, and goes
+// through the device split's lane code as an emulated wave (node_split_lanes.h,
+// node_split_wave_host.h: what edv_node_split_count_kernel and edv_node_split_emit_kernel run), at
+// the place in the buffer the entries before it give it; the verdict, the member count, the body
+// bytes and every member's span must equal node_split's.
 //
 // Corpus file: per text a little-endian uint32 length, then the bytes
 // (tools/wire_probe.py --write-corpus FILE / --write-node-corpus FILE write the test corpora).
@@ -24,6 +28,7 @@
 #include <vector>
 
 #include "node_split.h"
+#include "node_split_wave_host.h"
 #include "wire_idents.h"
 #include "wire_scan.h"
 #include "wire_unwrap.h"
@@ -96,8 +101,31 @@ bool unwrap_message(const uint8_t* body, uint32_t len, uint32_t esc, NodeCounts&
   return ok;
 }
 
+// The entry at [ea, ea + len) of the buffer through the emulated wave, against node_split's answer.
+bool lanes_equal(const uint8_t* entry, uint64_t ea, uint64_t len, bool split, const std::vector<edv::NodeSpan>& spans) {
+  const edv::EntryCount c = edv::lanes_count(entry, ea, ea + len);
+  uint64_t bytes = 0;
+  for (const edv::NodeSpan& s : spans) bytes += s.len;
+  if (c.split != split || c.members != (split ? spans.size() : 1) || c.bytes != (split ? bytes : len)) return false;
+  if (!split) return true;
+  uint64_t seen = 0, body = 0;
+  bool ok = true;
+  std::vector<uint8_t> met(spans.size(), 0);
+  edv::lanes_emit(entry, ea, ea + len, [&](uint64_t index, uint64_t at_body, uint64_t first) {
+    ok = ok && index < spans.size() && !met[index] && first == ea + spans[index].at;
+    if (!ok) return;
+    met[index] = 1;
+    uint64_t before = 0;
+    for (uint64_t j = 0; j < index; ++j) before += spans[j].len;
+    ok = at_body == before;
+    ++seen;
+    body += spans[index].len;
+  });
+  return ok && seen == spans.size() && body == bytes;
+}
+
 int node_main(FILE* f) {
-  uint64_t entries = 0, split = 0, messages = 0;
+  uint64_t entries = 0, split = 0, messages = 0, at = 0, lane_split = 0, lane_members = 0;
   NodeCounts as_cut, whole, escaped;
   for (;;) {
     uint8_t hdr[4];
@@ -120,7 +148,15 @@ int node_main(FILE* f) {
     ++entries;
     std::vector<edv::NodeSpan> spans;
     bool ok = true;
-    if (edv::node_split(entry, len, spans)) {
+    const bool is_split = edv::node_split(entry, len, spans);
+    if (!lanes_equal(entry, at, len, is_split, spans)) {
+      fprintf(stderr, "entry %llu: the lane code and node_split disagree\n", (unsigned long long)entries);
+      return 1;
+    }
+    at += len;
+    lane_split += is_split;
+    lane_members += is_split ? spans.size() : 0;
+    if (is_split) {
       ++split;
       for (const edv::NodeSpan& s : spans) {
         ok = ok && s.at + s.len <= len && unwrap_message(entry + s.at, (uint32_t)s.len, 1, as_cut);
@@ -139,6 +175,8 @@ int node_main(FILE* f) {
   }
   printf("entries %llu split %llu messages %llu\n", (unsigned long long)entries, (unsigned long long)split,
          (unsigned long long)messages);
+  printf("lane code: split %llu members %llu, equal to node_split on every entry\n", (unsigned long long)lane_split,
+         (unsigned long long)lane_members);
   const NodeCounts* rows[3] = {&as_cut, &whole, &escaped};
   const char* names[3] = {"as cut", "entries whole", "entries as escaped bodies"};
   for (int k = 0; k < 3; ++k)

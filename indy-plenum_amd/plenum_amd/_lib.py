@@ -67,6 +67,9 @@ SIGNATURES = {
     "edv_host_free": (_I, [_P]),
     "edv_wire_scan": (_I, [_P, _P, _P, _U64, _P, _P]),
     "edv_wire_scan_node": (_I, [_P, _P, _P, _P, _U64, _P, _P, _P]),
+    "edv_wire_scan_entries": (_I, [_P, _P, _P, _U64, _P, _P]),
+    "edv_wire_entries_result": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "edv_wire_raw_readback": (_I, [_P, _P]),
     "edv_wire_ident_text": (_I, [_P, _P, _U64, _P, _P]),
     "edv_wire_verify": (_I, [_P, _P, _P, _U64, _P]),
     "edv_wire_idents": (_I, [_P, _P, _P, _P]),

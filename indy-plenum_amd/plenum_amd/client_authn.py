@@ -350,6 +350,9 @@ class _GpuState:
         # the wire batch's distinct identifiers on the GPU (engine.wire_idents, on an engine with
         # supports_wire_idents); EDV_WIRE_IDENTS=0: the host pass (_hostpack.wire_idents), for A/B runs
         self.wire_idents_gpu = os.environ.get("EDV_WIRE_IDENTS", "1") != "0"
+        # a node drain's BATCHes split on the GPU (engine.wire_scan_entries, on an engine with
+        # supports_wire_split); EDV_WIRE_SPLIT=0: the host split (_hostpack.gather_node_texts)
+        self.wire_split_gpu = os.environ.get("EDV_WIRE_SPLIT", "0") != "0"
 
 
 class GpuAuthMixin:
@@ -1791,6 +1794,9 @@ class GpuAuthMixin:
 
         The host cuts the member strings out of each BATCH
         (_hostpack.gather_node_texts) and copies the bodies into pinned memory;
+        with EDV_WIRE_SPLIT=1, on an engine with supports_wire_split, it copies
+        the entries whole and the GPU cuts them out (engine.wire_scan_entries,
+        csrc/node_split_lanes.h).  Either way the messages are the same, and
         the GPU unescapes them, finds the request inside a PROPAGATE
         (edv_wire_unwrap_kernel, csrc/wire_unwrap.h) and scans and verifies it
         as authenticate_wire_batch does.  Messages outside that grammar (a
@@ -1833,24 +1839,38 @@ class GpuAuthMixin:
             return []
         with _engine_lock(eng):
             t0 = _perf_counter()
+            split_gpu = (g.wire_split_gpu and _gather_texts is not None
+                         and getattr(eng, "supports_wire_split", False))
+            # the host split copies the BATCH members' bodies, the GPU split the entries whole
+            gather = _gather_texts if split_gpu else _gather_node_texts
             buf = self._wire_text_buffer(eng, int(n_e * g.node_wire_bytes_per_entry) + 4096)
-            got = _gather_node_texts(entries, buf, g.scan_threads)
+            got = gather(entries, buf, g.scan_threads)
             if got is None:  # the estimate was short, or an entry is not bytes
                 if not all(t.__class__ is bytes for t in entries):
                     return None
                 buf = self._wire_text_buffer(eng, sum(map(len, entries)))
-                got = _gather_node_texts(entries, buf, g.scan_threads)
+                got = gather(entries, buf, g.scan_threads)
                 if got is None:
                     return None
-            off = np.frombuffer(got[0], np.uint64)
-            esc = np.frombuffer(got[1], np.uint8)
-            entry = np.frombuffer(got[2], np.uint32)
-            n = len(esc)
-            g.node_wire_bytes_per_entry = max(g.node_wire_bytes_per_entry * 0.5, int(off[-1]) / n_e * 1.1)
-            if n == 0:  # (nothing but empty BATCHes)
-                return [[] for _ in range(n_e)]
-            t1 = _perf_counter()
-            cls, status, span = eng.wire_scan_node(np.frombuffer(buf, np.uint8), off, esc)
+            if split_gpu:
+                entry_off = np.frombuffer(got, np.uint64)
+                g.node_wire_bytes_per_entry = max(g.node_wire_bytes_per_entry * 0.5, int(entry_off[-1]) / n_e * 1.1)
+                t1 = _perf_counter()
+                cls, status, span, esc, entry, at, off = eng.wire_scan_entries(np.frombuffer(buf, np.uint8), entry_off)
+                n = len(esc)
+                if n == 0:  # (nothing but empty BATCHes)
+                    return [[] for _ in range(n_e)]
+            else:
+                off = np.frombuffer(got[0], np.uint64)
+                esc = np.frombuffer(got[1], np.uint8)
+                entry = np.frombuffer(got[2], np.uint32)
+                at = off  # (the bodies lie in buf as the scan's offsets say)
+                n = len(esc)
+                g.node_wire_bytes_per_entry = max(g.node_wire_bytes_per_entry * 0.5, int(off[-1]) / n_e * 1.1)
+                if n == 0:  # (nothing but empty BATCHes)
+                    return [[] for _ in range(n_e)]
+                t1 = _perf_counter()
+                cls, status, span = eng.wire_scan_node(np.frombuffer(buf, np.uint8), off, esc)
             t2 = _perf_counter()
             # the identifier spans are relative to the unwrapped text, which only the GPU holds
             pinned = self._pinned(eng, "wire_uidx", 4 * n)
@@ -1862,7 +1882,7 @@ class GpuAuthMixin:
             g.stats["wire_items"] += n - int(np.count_nonzero(none)) - len(host)
             counts = np.bincount(entry[~none], minlength=n_e)
             if host:
-                self._node_wire_host(entries, buf, off, esc, entry, host, results, counts)
+                self._node_wire_host(entries, buf, off, at, esc, entry, host, results, counts)
                 flat = []
                 for i in np.flatnonzero(~none).tolist():
                     r = results[i]
@@ -1884,9 +1904,10 @@ class GpuAuthMixin:
                                      "items": n, "host_items": len(host)}
             return out
 
-    def _node_wire_host(self, entries, buf, off, esc, entry, host, results, counts):
+    def _node_wire_host(self, entries, buf, off, at, esc, entry, host, results, counts):
         """results[i] = the list of results of message i, for i in host, the host's
-        way: the entry itself, or the BATCH member turned back into its text and
+        way: the entry itself, or the BATCH member (its still escaped body lies at
+        buf[at[i]:], off[i + 1] - off[i] bytes) turned back into its text and
         visited one level down as in its BATCH; one authenticate_batch over all of
         them.  counts[e] (results per entry) is adjusted to what they yield."""
         import json
@@ -1895,7 +1916,7 @@ class GpuAuthMixin:
         found = []
         for i in host:
             if esc[i]:
-                body = bytes(text[int(off[i]):int(off[i + 1])])
+                body = bytes(text[int(at[i]):int(at[i]) + int(off[i + 1]) - int(off[i])])
                 found.append(requests_in_drain([{"op": "BATCH", "messages": [json.loads(b'"' + body + b'"')]}]))
             else:
                 found.append(requests_in_drain([entries[entry[i]]]))

@@ -370,6 +370,49 @@ class EdVerifyEngine:
         self._wire_span = span
         return cls, status, span
 
+    supports_wire_split = True
+
+    def wire_scan_entries(self, text, entry_off):
+        """wire_scan_node over a node stack's rxMsgs entries, uploaded whole
+        (entry e = text[entry_off[e] : entry_off[e + 1]]; host_alloc memory is
+        DMA'd in place): the GPU cuts each BATCH's member strings out
+        (edv_wire_scan_entries, csrc/node_split_lanes.h) exactly as
+        _hostpack.gather_node_texts does on the host.  Returns (cls, status,
+        idr_span as wire_scan_node, esc uint8[m], entry uint32[m], at
+        uint64[m] -- the position of message i's first byte in text --, off
+        uint64[m + 1] from 0 -- message i is off[i + 1] - off[i] bytes)."""
+        text = text if isinstance(text, np.ndarray) and text.dtype == np.uint8 else np.frombuffer(text, np.uint8)
+        entry_off = np.ascontiguousarray(entry_off, dtype=np.uint64)
+        n_e = entry_off.shape[0] - 1
+        if n_e < 0:
+            raise ValueError("entry_off needs n + 1 entries")
+        if int(entry_off[-1]) > text.shape[0]:
+            raise ValueError("entry_off exceeds the text buffer")
+        m, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(self._lib.edv_wire_scan_entries(self._ctx, _ptr(text) if text.size else None, _ptr(entry_off), n_e,
+                                              ctypes.byref(m), ctypes.byref(nbytes)))
+        m = m.value
+        cls = np.ones(m, np.uint8)
+        status = np.ones(m, np.uint8)
+        span = np.zeros((m, 2), np.uint32)
+        esc = np.zeros(m, np.uint8)
+        entry = np.zeros(m, np.uint32)
+        at = np.zeros(m, np.uint64)
+        off = np.zeros(m + 1, np.uint64)
+        p = (lambda a: _ptr(a)) if m else (lambda a: None)
+        check(self._lib.edv_wire_entries_result(self._ctx, p(cls), p(status), p(span), p(esc), p(entry), p(at),
+                                                _ptr(off)))
+        self._wire_shape = (m, nbytes.value)
+        self._wire_span = span
+        return cls, status, span, esc, entry, at, off
+
+    def wire_raw_readback(self):
+        """DIAGNOSTIC (edv_wire_raw_readback): the message bodies the last
+        wire_scan_entries put back to back in HBM, uint8[off[m]]."""
+        raw = np.zeros(getattr(self, "_wire_shape", (0, 0))[1], np.uint8)
+        check(self._lib.edv_wire_raw_readback(self._ctx, _ptr(raw) if raw.size else None))
+        return raw
+
     def wire_ident_text(self, uniq_item):
         """The identifiers (bytes each) of the wire batch's items uniq_item, read
         out of the text the scan saw in HBM (edv_wire_ident_text): after

@@ -14,11 +14,12 @@ found on the GPU (EDV_WIRE_IDENTS=1: edv_wire_idents, edv_wire_verify_idents) an
 
 --node: a node stack's drain (nodeloop.drain_texts: per group of --members requests, one BATCH of
 their PROPAGATEs from each of the other pool - 1 nodes), about --n signed requests in all, for a
-4-node and a 25-node pool, three ways alternating in one process:
-  (a) authenticate_node_wire_batch(entries)                          split, unwrapped and scanned on the GPU
+4-node and a 25-node pool, four ways alternating in one process:
+  (a) authenticate_node_wire_batch(entries), EDV_WIRE_SPLIT=0        split on the host, unwrapped and scanned on the GPU
+  (a') the same with EDV_WIRE_SPLIT=1 (node_wire_split)              the entries copied whole, split on the GPU too
   (b) authenticate_batch(batching.requests_in_drain(entries))        what a node pays today
   (c) authenticate_wire_batch(the bare client texts, same requests)  the scan's own cost, no unwrap
-with the results asserted equal; p50 and min-max per path and per phase of (a) and (c).
+with the results asserted equal in every batch; p50 and min-max per path and per phase of (a), (a') and (c).
 
 usage: python tools/wire_probe.py [--n 1000000] [--signers 1000] [--batches 10] [--out FILE] [--idents-ab | --node]
        python tools/wire_probe.py --write-corpus FILE        (no GPU: the test corpora, length-prefixed,
@@ -132,10 +133,12 @@ def node_probe(eng, args, texts, dicts, idrs, vks):
     from plenum_amd import nodeloop
     from plenum_amd.batching import requests_in_drain
     from plenum_amd.client_authn import GpuAuthNr
-    a = GpuAuthNr(engine=eng)
-    for idr, vk in zip(idrs, vks):
-        a.addIdr(idr, vk)
-    a.keys_settle()
+    a, a_split = GpuAuthNr(engine=eng), GpuAuthNr(engine=eng)
+    a._g.wire_split_gpu, a_split._g.wire_split_gpu = False, True
+    for x in (a, a_split):
+        for idr, vk in zip(idrs, vks):
+            x.addIdr(idr, vk)
+        x.keys_settle()
     phases = ("gather", "scan", "keys", "verify", "results")
     out = {"n": args.n, "signers": args.signers, "batches": args.batches, "members": args.members, "pools": {}}
     for pool in (4, 25):
@@ -148,14 +151,15 @@ def node_probe(eng, args, texts, dicts, idrs, vks):
             bare += [texts[i] for i in group] * (pool - 1)
         paths = {
             "node_wire": lambda: a.authenticate_node_wire_batch(entries),
+            "node_wire_split": lambda: a_split.authenticate_node_wire_batch(entries),
             "loads_dicts": lambda: a.authenticate_batch(requests_in_drain(entries)),
             "bare_wire": lambda: a.authenticate_wire_batch(bare),
         }
         for f in paths.values():  # warm-up: buffers grown, kernels loaded
             f()
-        host0 = a.stats["wire_host_items"]
+        host0 = a.stats["wire_host_items"], a_split.stats["wire_host_items"]
         times = {k: [] for k in paths}
-        breakdown = {"node_wire": [], "bare_wire": []}
+        breakdown = {"node_wire": [], "node_wire_split": [], "bare_wire": []}
         for _ in range(args.batches):
             res = {}
             for name, f in paths.items():
@@ -163,13 +167,15 @@ def node_probe(eng, args, texts, dicts, idrs, vks):
                 res[name] = f()
                 times[name].append((time.perf_counter() - t0) * 1e3)
                 if name in breakdown:
-                    breakdown[name].append(dict(a._g.last_wire_breakdown))
+                    breakdown[name].append(dict((a_split if name == "node_wire_split" else a)._g.last_wire_breakdown))
+            assert res["node_wire"] == res["node_wire_split"], "results differ between the host and the GPU split"
             flat = [r for per in res["node_wire"] for r in per]  # (per entry: flattened outside the timing)
             assert flat == res["loads_dicts"] == res["bare_wire"], "results differ between the paths"
             assert len(flat) == len(bare) and all(r.__class__ is str for r in flat)
             del flat
             del res
-        assert a.stats["wire_host_items"] == host0, "the GPU left messages to the host"
+        assert (a.stats["wire_host_items"], a_split.stats["wire_host_items"]) == host0, \
+            "the GPU left messages to the host"
         row = {"entries": len(entries), "requests": len(bare), "entry_bytes": sum(map(len, entries)),
                "bare_bytes": sum(map(len, bare))}
         for name, ts in times.items():
@@ -179,6 +185,7 @@ def node_probe(eng, args, texts, dicts, idrs, vks):
         p50 = {k: row[k]["batch_ms"]["p50"] for k in paths}
         row["a_over_b"] = round(p50["node_wire"] / p50["loads_dicts"], 4)
         row["a_minus_c_ms"] = round(p50["node_wire"] - p50["bare_wire"], 3)
+        row["split_minus_a_ms"] = round(p50["node_wire_split"] - p50["node_wire"], 3)
         out["pools"][str(pool)] = row
         print("pool %d: %s" % (pool, json.dumps(row)), flush=True)
         del entries, bare
