@@ -46,8 +46,10 @@ def _check_against_twin(eng, hostcheck, texts, base):
 
 @pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 4096])
 def test_scan_equals_cpu_twin(gpu_engine, hostcheck, n):
-    """Shuffled corpus texts: 10-byte and 4 KiB items share LDS tiles, items straddle tile
-    boundaries, over-long items sit between scanned ones."""
+    """Shuffled corpus texts: 10-byte and 4 KiB items share an LDS tile, over-long items sit
+    between scanned ones.  At 253 bytes a text on average the 64 items of a workgroup always end
+    inside its first tile (tests/test_wire_tile_layouts.py asserts it); the second tile and the
+    tile edges are tests/test_gpu_wire_tiles.py's."""
     r = random.Random(100 + n)
     texts = r.choices(wire_model.corpus(), k=n)
     status = _check_against_twin(gpu_engine, hostcheck, texts, 0)
