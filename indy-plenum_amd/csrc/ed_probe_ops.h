@@ -6,8 +6,11 @@
 //
 // An item of op OP is lane_in_words(OP) input words and lane_out_words(OP) output words; field
 // elements are 10 raw limbs (not reduced: the tests pass limbs at the class bounds), points are
-// X, Y, Z, T (40 words), niels entries y+x, y-x, 2dxy (30 words), byte strings 8 LE words.
+// X, Y, Z, T (40 words), niels entries y+x, y-x, 2dxy (30 words), byte strings 8 LE words, a
+// signature slot (sig_slot.h) its 24 LE words.
 #pragma once
+#include "key_dedup.h"
+#include "sig_slot.h"
 #include "verify_core.h"
 
 namespace edv {
@@ -18,7 +21,7 @@ enum : int {
   kFePow22523, kFeIszero, kFeIsnegative, kFeCmov,
   kScReduce, kScIsCanonical, kScMuladd, kRecode16, kComb10, kComb14, kComb16, kCombBase,
   kGeFrombytes, kHasSmallOrder, kIsCanonicalPoint, kGeAdd, kGeSub, kGeMadd, kGeMsub, kGeAddSigned, kP2Dbl, kP3Dbl,
-  kCombSetEntry, kGeTobytes,
+  kCombSetEntry, kGeTobytes, kSigSlot,
   kLaneOps
 };
 constexpr int kCombOutWords = 27;  // the row count, then up to 26 digits (W = 10), zero past the rows
@@ -32,6 +35,7 @@ EDV_HD constexpr int lane_in_words(int op) {
     case kCombBase: case kHasSmallOrder: case kIsCanonicalPoint: return 8;
     case kScReduce: return 16;
     case kScMuladd: return 24;     // a, b, c
+    case kSigSlot: return 24;      // an EDV_SIG_SLOT96 slot
     case kGeFrombytes: return 9;   // s, negate
     case kGeAdd: case kGeSub: return 80;  // p (p3), q (p3: made cached as the callers do)
     case kGeMadd: case kGeMsub: return 70;  // p (p3), q (niels)
@@ -47,6 +51,7 @@ EDV_HD constexpr int lane_out_words(int op) {
     case kFeTobytes: case kScReduce: case kScMuladd: case kGeTobytes: return 8;
     case kFeIszero: case kFeIsnegative: case kScIsCanonical: case kHasSmallOrder: case kIsCanonicalPoint: return 1;
     case kRecode16: return 64;
+    case kSigSlot: return 16;  // R || S
     case kComb10: case kComb14: case kComb16: case kCombBase: return kCombOutWords;
     case kGeFrombytes: return 41;  // ok, then the point
     case kGeAdd: case kGeSub: case kGeMadd: case kGeMsub: case kGeAddSigned: case kP2Dbl: case kP3Dbl:
@@ -156,6 +161,10 @@ EDV_HD void lane_op(const uint32_t* in, uint32_t* out) {
     uint32_t o[8];
     ge_tobytes(o, q);
     for (int k = 0; k < 8; ++k) out[k] = o[k];
+  } else if constexpr (OP == kSigSlot) {
+    uint32_t o[16];
+    sig_slot_decode(o, w);
+    for (int k = 0; k < 16; ++k) out[k] = o[k];
   } else if constexpr (OP == kCombSetEntry) {
     ge_niels nb;
     load_niels(nb, in);
@@ -213,11 +222,20 @@ EDV_HD bool hash_op(int form, uint32_t h[8], const uint32_t sig[16], const uint3
   return verify_phase_hash_units(h, sig, pk, units, 1, mlen);
 }
 
+// The distinct-key dedupe of one sub-batch (key_dedup.h: dedup_insert for every request, then
+// dedup_assign for every request, as edv_dedup_insert_kernel and edv_dedup_assign_kernel run
+// them).  Both entry points refuse, before they run anything, a batch whose table could fill up
+// or whose probe walk could be long: no request, fewer slots than requests, more than 4096.
+constexpr uint64_t kDedupMaxN = 4096;
+inline bool dedup_args_ok(uint64_t n, uint64_t nslots) {
+  return n >= 1 && n <= kDedupMaxN && nslots >= n && nslots <= 2 * kDedupMaxN;
+}
+
 // X(op) for every lane op, for the switches of the two builds
 #define EDV_ED_LANE_OPS(X)                                                                                         \
   X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) \
-  X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32) X(33) X(34)
-static_assert(kLaneOps == 35, "EDV_ED_LANE_OPS lists every op");
+  X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32) X(33) X(34) X(35)
+static_assert(kLaneOps == 36, "EDV_ED_LANE_OPS lists every op");
 
 }  // namespace edp
 }  // namespace edv

@@ -53,7 +53,9 @@
 #include "batch_encode.h"
 #include "comb.h"
 #include "fe_lanes.h"
+#include "key_dedup.h"
 #include "sha256.h"
+#include "sig_slot.h"
 #include "verify_core.h"
 #include "node_split_lanes.h"
 #include "wire_idents.h"
@@ -192,58 +194,15 @@ __device__ __forceinline__ uint64_t hash_lane_request(uint64_t t, const uint32_t
 // (hostpack.cpp b58_len64), so its value is < 2^512 and the decode is the
 // 512-bit big-endian value of the text; t == 0: bytes 0..63 are R || S
 // (decoded on the host: other lengths, which move bytes across the split at
-// 64).  HBM: 96 B read + 64 B written per request.
-__device__ __forceinline__ uint32_t b58_digit(uint32_t c) {
-  // '1'-'9' 0-8, 'A'-'H' 9-16, 'J'-'N' 17-21, 'P'-'Z' 22-32, 'a'-'k' 33-43, 'm'-'z' 44-57
-  uint32_t d = c - '1';
-  d = c >= 'A' ? c - 'A' + 9 - (c > 'H') - (c > 'N') : d;
-  d = c >= 'a' ? c - 'a' + 33 - (c > 'k') : d;
-  return d;
-}
-
-constexpr uint32_t kPow58[6] = {1u, 58u, 3364u, 195112u, 11316496u, 656356768u};
-
+// 64).  HBM: 96 B read + 64 B written per request.  The decode is sig_slot.h's.
 __global__ __launch_bounds__(kBlock) void edv_b58_sig_kernel(const uint8_t* __restrict__ slots, uint64_t n,
                                                             uint8_t* __restrict__ sig64) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t w[24];
   load_words(w, slots + 96 * i, 24);
-  const uint32_t t = w[23] >> 24;
   uint32_t out[16];
-  if (t == 0) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) out[j] = w[j];
-  } else {
-    // Horner over groups of five digits (58^5 < 2^32): acc = acc * 58^k + chunk,
-    // k = the group's digits inside the text (0..5, per lane)
-    uint32_t acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0;
-#pragma unroll
-    for (int g = 0; g < 19; ++g) {
-      uint32_t chunk = 0, k = 0;
-#pragma unroll
-      for (int q = 0; q < 5; ++q) {
-        const int p = 5 * g + q;
-        if (p < 95 && (uint32_t)p < t) {
-          chunk = chunk * 58u + b58_digit((w[p >> 2] >> (8 * (p & 3))) & 0xffu);
-          ++k;
-        }
-      }
-      const uint32_t mul = k == 5 ? kPow58[5] : k == 4 ? kPow58[4] : k == 3 ? kPow58[3] : k == 2 ? kPow58[2]
-                         : k == 1 ? kPow58[1] : kPow58[0];
-      uint64_t carry = chunk;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const uint64_t v = (uint64_t)acc[j] * mul + carry;
-        acc[j] = (uint32_t)v;
-        carry = v >> 32;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 16; ++j) out[j] = __builtin_bswap32(acc[15 - j]);  // big-endian bytes
-  }
+  sig_slot_decode(out, w);
   uint4* o = (uint4*)(sig64 + 64 * i);
 #pragma unroll
   for (int k = 0; k < 4; ++k) o[k] = make_uint4(out[4 * k], out[4 * k + 1], out[4 * k + 2], out[4 * k + 3]);
@@ -341,55 +300,16 @@ __global__ __launch_bounds__(kBlock, EDV_HASH_MIN_WAVES) void edv_hash_kernel(co
 #ifndef EDV_TABLE_MIN_WAVES
 #define EDV_TABLE_MIN_WAVES 2  // 168 VGPRs (+spill) beats 256+256 AGPRs at 1 wave: table -8%
 #endif
-// ---- general path, distinct keys of a sub-batch: the table kernel decodes
-// each distinct 32-byte key once (a batch of 1M requests from 1,000 signers
-// builds 1,000 tables, not 1M).  Open-addressing hash table over the
-// sub-batch: slot = request index of the key's representative (0xffffffff =
-// empty); the full 32 bytes are compared, so distinct keys never share a
-// table whatever their hash.  Which request becomes the representative
-// depends on the order of the atomics; the table -- a function of the key
-// bytes only -- does not.
-constexpr uint32_t kEmptySlot = 0xffffffffu;
-__device__ __forceinline__ uint32_t key_hash(const uint32_t pk[8]) {
-  uint32_t h = pk[0] * 0x9e3779b1u;
-  h ^= pk[1] * 0x85ebca77u;
-  h ^= (pk[2] ^ pk[5]) * 0xc2b2ae3du;
-  h ^= (pk[3] ^ pk[7]) * 0x27d4eb2fu;
-  return h ^ (h >> 15);
-}
-__device__ __forceinline__ bool same_key(const uint8_t* __restrict__ pk32, uint64_t a, const uint32_t pk[8]) {
-  uint32_t w[8];
-  load_words(w, pk32 + 32 * a, 8);
-  bool eq = true;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) eq = eq && w[k] == pk[k];
-  return eq;
-}
-// slot of request i's key (inserting i as the representative if new)
-__device__ uint32_t dedup_slot(const uint8_t* __restrict__ pk32, uint64_t i, uint32_t* __restrict__ slots,
-                               uint32_t nslots, bool insert) {
-  uint32_t pk[8];
-  load_words(pk, pk32 + 32 * i, 8);
-  uint32_t h = key_hash(pk) % nslots;
-  for (uint32_t probe = 0; probe < nslots; ++probe) {
-    uint32_t s = __atomic_load_n(&slots[h], __ATOMIC_RELAXED);
-    if (s == kEmptySlot) {
-      if (!insert) return kEmptySlot;  // unreachable after the insert pass
-      s = atomicCAS(&slots[h], kEmptySlot, (uint32_t)i);
-      if (s == kEmptySlot) return h;
-    }
-    if (s == (uint32_t)i || same_key(pk32, s, pk)) return h;
-    h = h + 1 == nslots ? 0 : h + 1;
-  }
-  return kEmptySlot;  // table full: impossible with nslots = 2n
-}
+// ---- general path, distinct keys of a sub-batch (key_dedup.h: the hash
+// table, its two passes and split_of, the tables per distinct key).
+static_assert(kDedupBlock == kBlock, "key_dedup.h names this file's block size");
 // every request records its key's slot
 __global__ __launch_bounds__(kBlock) void edv_dedup_insert_kernel(const uint8_t* __restrict__ pk32, uint64_t n,
                                                                  uint32_t* __restrict__ slots, uint32_t nslots,
                                                                  uint32_t* __restrict__ req_slot) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  req_slot[i] = dedup_slot(pk32, i, slots, nslots, true);
+  dedup_insert(pk32, i, slots, nslots, req_slot);
 }
 // representative -> compact key index u (reps[u] = its request)
 __global__ __launch_bounds__(kBlock) void edv_dedup_assign_kernel(uint64_t n, const uint32_t* __restrict__ slots,
@@ -399,22 +319,7 @@ __global__ __launch_bounds__(kBlock) void edv_dedup_assign_kernel(uint64_t n, co
                                                                  uint32_t* __restrict__ count) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint32_t h = req_slot[i];
-  if (slots[h] == (uint32_t)i) {
-    const uint32_t u = atomicAdd(count, 1u);
-    slot_u[h] = u;
-    reps[u] = (uint32_t)i;
-  }
-}
-
-// Tables per distinct key: K = 8 with at least 16 requests per distinct key
-// in the sub-batch, K = 4 with at least 4, else 1.  The K tables of all keys
-// then fit the sub-batch's scratch (K * count <= n), and the 256 (K-1)/K
-// extra doublings per key cost at most 256 (K-1)/K^2 per request against
-// 256 (K-1)/K saved in every ladder.  Decided on the device from the
-// distinct-key count, identically by the table and ladder kernels.
-__device__ __forceinline__ int split_of(uint32_t count, uint64_t n) {
-  return 16ull * count <= n ? 8 : 4ull * count <= n ? 4 : 1;
+  dedup_assign(i, slots, req_slot, slot_u, reps, count);
 }
 
 // Tables of distinct key u (u < *count): decode -A of request reps[u]'s key,

@@ -849,4 +849,28 @@ int edv_host_ed_hash(int form, const uint8_t* sig64, const uint8_t* pk32, const 
   free(b);
   return 0;
 }
+// the dedupe of edprobe_dedup with the requests taken one after the other (key_dedup.h's host
+// build: plain loads and stores)
+int edv_host_ed_dedup(const uint8_t* pk32, uint64_t n, uint64_t nslots, uint32_t* slots, uint32_t* req_slot,
+                      uint32_t* slot_u, uint32_t* reps, uint32_t* count, uint32_t* hashes, int* split) {
+  if (!edv::edp::dedup_args_ok(n, nslots)) return -1;
+  uint8_t* keys = (uint8_t*)aligned_alloc(16, 32 * n);
+  if (!keys) return -2;
+  memcpy(keys, pk32, 32 * n);
+  memset(slots, 0xff, 4 * nslots);
+  memset(req_slot, 0xff, 4 * n);
+  memset(slot_u, 0xff, 4 * nslots);
+  memset(reps, 0xff, 4 * n);
+  *count = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    uint32_t pk[8];
+    edv::load_key(pk, keys, i);
+    hashes[i] = edv::key_hash(pk);
+    edv::dedup_insert(keys, i, slots, (uint32_t)nslots, req_slot);
+  }
+  for (uint64_t i = 0; i < n; ++i) edv::dedup_assign(i, slots, req_slot, slot_u, reps, count);
+  *split = edv::split_of(*count, n);
+  free(keys);
+  return 0;
+}
 }  // extern "C"

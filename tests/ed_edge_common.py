@@ -31,7 +31,7 @@ LANE_OPS = ["fe_mul", "fe_sq", "fe_sqn", "fe_add", "fe_sub", "fe_sub4", "fe_neg"
             "fe_frombytes", "fe_invert", "fe_pow22523", "fe_iszero", "fe_isnegative", "fe_cmov",
             "sc_reduce", "sc_is_canonical", "sc_muladd", "recode16", "comb10", "comb14", "comb16", "comb_base",
             "ge_frombytes", "has_small_order", "is_canonical_point", "ge_add", "ge_sub", "ge_madd", "ge_msub",
-            "ge_add_signed", "p2_dbl", "p3_dbl", "comb_set_entry", "ge_tobytes"]
+            "ge_add_signed", "p2_dbl", "p3_dbl", "comb_set_entry", "ge_tobytes", "sig_slot"]
 OP = {name: i for i, name in enumerate(LANE_OPS)}
 WAVE_OPS = ["dist_sq", "dist_mul", "dist_sqn", "cols_carry", "dist_round", "r_decode", "tree_sum"]
 WOP = {name: i for i, name in enumerate(WAVE_OPS)}
@@ -789,3 +789,60 @@ def check_tree_sum(pr, width):
             assert affine_of(o) == w, (width, junk, i)
         n += len(rows)
     return n
+
+
+# ---- signature slots (csrc/sig_slot.h: the body of edv_b58_sig_kernel)
+B58 = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"
+
+
+def b58encode(raw):
+    """the base58 text of raw: a '1' per leading zero byte, then the digits of the rest's value"""
+    nz = len(raw) - len(raw.lstrip(b"\0"))
+    v, digits = int.from_bytes(raw, "big"), ""
+    while v:
+        v, r = divmod(v, 58)
+        digits = B58[r] + digits
+    return "1" * nz + digits
+
+
+def sig_slot_values():
+    """64-byte signatures with nz = 0..64 leading zero bytes: the smallest and the largest value of
+    the other L = 64 - nz bytes, 01 ff.., ff 00.. and 20 random ones with a non-zero top byte"""
+    rng = random.Random(58)
+    out = []
+    for nz in range(65):
+        n = 64 - nz
+        if n == 0:
+            out.append(bytes(64))
+            continue
+        tails = [b"\x01" + bytes(n - 1), b"\xff" * n, b"\x01" + b"\xff" * (n - 1), b"\xff" + bytes(n - 1)]
+        tails += [bytes([rng.randrange(1, 256)]) + bytes(rng.getrandbits(8) for _ in range(n - 1)) for _ in range(20)]
+        out += [bytes(nz) + t for t in tails]
+    return out
+
+
+def sig_slot_text_lengths(values):
+    return [len(b58encode(v)) for v in values]
+
+
+def check_sig_slot(pr):
+    """A text slot decodes to the 64 bytes it encodes, whatever follows the text up to byte 95; a
+    raw slot (byte 95 = 0) passes its first 64 bytes through, whatever bytes 64..94 hold."""
+    values = sig_slot_values()
+    rng = random.Random(59)
+    rows, want = [], []
+    for v in values:
+        text = b58encode(v).encode()
+        assert 64 <= len(text) <= 88
+        for fill in (b"\0", b"z"):
+            rows.append(text + fill * (95 - len(text)) + bytes([len(text)]))
+            want.append(v)
+    for v in values[::7] + [b"\xff" * 64, bytes(64)]:
+        for fill in (bytes(31), b"z" * 31, bytes(rng.getrandbits(8) for _ in range(31))):
+            rows.append(v + fill + b"\0")
+            want.append(v)
+    a = np.frombuffer(b"".join(rows), "<u4").reshape(len(rows), 24)
+    got = pr.lane("sig_slot", a).astype("<u4")
+    for i, v in enumerate(want):
+        assert got[i].tobytes() == v, (i, rows[i][95], rows[i][:rows[i][95]], v.hex(), got[i].tobytes().hex())
+    return len(rows)

@@ -3,6 +3,8 @@
 // never loads it.  Two kernel shapes: one item per lane (csrc/ed_probe_ops.h, the body shared with
 // the CPU twins edv_host_ed_lane / edv_host_ed_hash of csrc/host_check.cpp) and one item per wave
 // (csrc/fe_lanes.h and csrc/small_lanes.h: device only, every lane's words copied in and out).
+// edprobe_dedup runs the general path's distinct-key dedupe (csrc/key_dedup.h) over one sub-batch
+// as the product launches it and returns its arrays (CPU twin: edv_host_ed_dedup).
 //
 // Host-pointer entry points: each allocates, launches one kernel (block 64), copies back and
 // returns the HIP error code (0 = hipSuccess); -1 for an argument the kernel must not see (an
@@ -70,6 +72,33 @@ __global__ __launch_bounds__(kBlock) void edprobe_hash_lanes_kernel(const uint32
     for (int k = 0; k < 8; ++k) h_out[8 * i + k] = h[k];
     ok_out[i] = ok ? 1 : 0;
   }
+}
+
+// the distinct-key dedupe as the product launches it: insert over every request, then assign
+__global__ __launch_bounds__(kDedupBlock) void edprobe_dedup_insert_kernel(const uint8_t* __restrict__ pk32, uint64_t n,
+                                                                          uint32_t* __restrict__ slots,
+                                                                          uint32_t nslots,
+                                                                          uint32_t* __restrict__ req_slot,
+                                                                          uint32_t* __restrict__ hashes) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t pk[8];
+  load_key(pk, pk32, i);
+  hashes[i] = key_hash(pk);
+  dedup_insert(pk32, i, slots, nslots, req_slot);
+}
+__global__ __launch_bounds__(kDedupBlock) void edprobe_dedup_assign_kernel(uint64_t n, const uint32_t* __restrict__ slots,
+                                                                          const uint32_t* __restrict__ req_slot,
+                                                                          uint32_t* __restrict__ slot_u,
+                                                                          uint32_t* __restrict__ reps,
+                                                                          uint32_t* __restrict__ count) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  dedup_assign(i, slots, req_slot, slot_u, reps, count);
+}
+// after the assign pass: the split the table and ladder kernels take
+__global__ void edprobe_split_kernel(const uint32_t* __restrict__ count, uint64_t n, int* __restrict__ split) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *split = split_of(*count, n);
 }
 
 // ---- one item per wave.  Words per item in / out:
@@ -242,6 +271,50 @@ int edprobe_hash(int form, const uint8_t* sig64, const uint8_t* pk32, const uint
   PROBE_TRY(hipGetLastError());
   PROBE_TRY(hipMemcpy(h_out, d_h, 32 * n, hipMemcpyDeviceToHost));
   PROBE_TRY(hipMemcpy(ok_out, d_ok, n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The distinct-key dedupe of one sub-batch of n requests (keys pk32, 32 bytes each) over nslots
+// slots, with the product's kernels' bodies and block size (csrc/key_dedup.h): slots cleared to
+// 0xff, the insert pass, the assign pass.  Out: slots[nslots], req_slot[n], slot_u[nslots] (0xff
+// where no representative wrote), reps[n] (0xff past the count), the distinct count, key_hash of
+// every request's key and split_of(count, n).  -1 without a launch for n == 0, nslots < n or
+// n > 4096 (edp::dedup_args_ok).
+int edprobe_dedup(const uint8_t* pk32, uint64_t n, uint64_t nslots, uint32_t* slots, uint32_t* req_slot,
+                  uint32_t* slot_u, uint32_t* reps, uint32_t* count, uint32_t* hashes, int* split) {
+  if (!edp::dedup_args_ok(n, nslots)) return -1;
+  Bufs bufs;
+  void *d_pk, *d_slots, *d_req, *d_su, *d_reps, *d_count, *d_hash, *d_split;
+  PROBE_TRY(bufs.copy_in(&d_pk, pk32, 32 * n));
+  PROBE_TRY(bufs.alloc(&d_slots, 4 * nslots));
+  PROBE_TRY(bufs.alloc(&d_req, 4 * n));
+  PROBE_TRY(bufs.alloc(&d_su, 4 * nslots));
+  PROBE_TRY(bufs.alloc(&d_reps, 4 * n));
+  PROBE_TRY(bufs.alloc(&d_count, 4));
+  PROBE_TRY(bufs.alloc(&d_hash, 4 * n));
+  PROBE_TRY(bufs.alloc(&d_split, sizeof(int)));
+  PROBE_TRY(hipMemset(d_slots, 0xff, 4 * nslots));
+  PROBE_TRY(hipMemset(d_req, 0xff, 4 * n));
+  PROBE_TRY(hipMemset(d_su, 0xff, 4 * nslots));
+  PROBE_TRY(hipMemset(d_reps, 0xff, 4 * n));
+  PROBE_TRY(hipMemset(d_count, 0, 4));
+  PROBE_TRY(hipMemset(d_split, 0, sizeof(int)));
+  const dim3 grid((uint32_t)((n + kDedupBlock - 1) / kDedupBlock)), block(kDedupBlock);
+  hipLaunchKernelGGL(edprobe_dedup_insert_kernel, grid, block, 0, 0, (const uint8_t*)d_pk, n, (uint32_t*)d_slots,
+                     (uint32_t)nslots, (uint32_t*)d_req, (uint32_t*)d_hash);
+  PROBE_TRY(hipGetLastError());
+  hipLaunchKernelGGL(edprobe_dedup_assign_kernel, grid, block, 0, 0, n, (const uint32_t*)d_slots,
+                     (const uint32_t*)d_req, (uint32_t*)d_su, (uint32_t*)d_reps, (uint32_t*)d_count);
+  PROBE_TRY(hipGetLastError());
+  hipLaunchKernelGGL(edprobe_split_kernel, dim3(1), dim3(kBlock), 0, 0, (const uint32_t*)d_count, n, (int*)d_split);
+  PROBE_TRY(hipGetLastError());
+  PROBE_TRY(hipMemcpy(slots, d_slots, 4 * nslots, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(req_slot, d_req, 4 * n, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(slot_u, d_su, 4 * nslots, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(reps, d_reps, 4 * n, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(count, d_count, 4, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(hashes, d_hash, 4 * n, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(split, d_split, sizeof(int), hipMemcpyDeviceToHost));
   return 0;
 }
 

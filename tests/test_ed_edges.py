@@ -71,5 +71,16 @@ def test_hash_refuses_the_wave_form_and_a_message_outside_its_buffer(twin):
                         ctypes.c_uint64(1), None, None) == -1
 
 
+def test_sig_slot_texts_cover_every_length_and_group_residue():
+    """The cases of check_sig_slot: text lengths 64..88, so every residue of the 5-digit Horner
+    groups (csrc/sig_slot.h), and every count of leading zero bytes."""
+    lens = set(ec.sig_slot_text_lengths(ec.sig_slot_values()))
+    assert lens == set(range(64, 89)) and {n % 5 for n in lens} == {0, 1, 2, 3, 4}
+
+
+def test_sig_slot_decode(twin):
+    assert ec.check_sig_slot(twin) > 3000
+
+
 def test_lane_model_is_exact_on_the_device_tables():
     assert ec.check_model_exact() > 1000

@@ -8,12 +8,16 @@ rootless encodings, the group operations on every pair of a set with torsion, P 
 the wave forms of the single-request kernels (csrc/fe_lanes.h, csrc/small_lanes.h) limb for limb
 against the model of tests/test_fe_lanes_model.py, R's decode against the one-lane decoder, the
 hash on the lanes at every pass edge and alignment, the tree sum at every lane position.  The
-tables and references are tests/ed_edge_common.py's; a failure here alone is the device's."""
+tables and references are tests/ed_edge_common.py's; a failure here alone is the device's.  Also
+the signature slots' base58 decode (csrc/sig_slot.h) on every text length and leading-zero count,
+and the general path's distinct-key dedupe (csrc/key_dedup.h) with the device's atomics against
+the model of tests/dedup_cases.py."""
 import ctypes
 import os
 
 import pytest
 
+import dedup_cases as dc
 import ed_edge_common as ec
 from conftest import PKG
 
@@ -100,3 +104,51 @@ def test_r_decode_on_lanes_equals_the_one_lane_decoder(probe):
 @pytest.mark.parametrize("width", [16, 32, 64])
 def test_tree_sum(probe, width):
     assert ec.check_tree_sum(probe, width) > 2 * width
+
+
+def test_sig_slot_decode(probe):
+    assert ec.check_sig_slot(probe) > 3000
+
+
+@pytest.fixture(scope="module")
+def dedup(gpu_engine):
+    return dc.Dedup(ctypes.CDLL(os.path.join(PKG, "libedv_ed_probe.so")), "edprobe")
+
+
+@pytest.fixture(scope="module")
+def dedup_twin(hostcheck):
+    return dc.Dedup(hostcheck, "edv_host_ed")
+
+
+def test_dedup_entry_refuses_without_a_launch(dedup):
+    k = [bytes(32)]
+    assert dedup.call([], 16)[0] == -1 and dedup.call(k * 8, 7)[0] == -1 and dedup.call(k * 4097, 8194)[0] == -1
+
+
+def test_dedup_multisets_meet_the_model(dedup, dedup_twin):
+    """The cases of tests/test_key_dedup.py with the device's atomics: the model's invariants (the
+    order of the inserts is free), and key_hash word for word the twin's."""
+    for name, keys, nslots in dc.multiset_cases():
+        r = dedup.run(keys, nslots)
+        dc.check_model(keys, r, nslots)
+        assert (r.hashes == dedup_twin.run(keys, nslots).hashes).all(), name
+
+
+def test_dedup_wrap_and_chain_families(dedup, dedup_twin):
+    pool = dc.family_pool()
+    want = dedup_twin.hashes(pool)
+    assert dedup.hashes(pool) == want
+    dc.check_families(dedup, want)
+
+
+def test_dedup_keys_one_word_apart_on_one_home_slot(dedup, dedup_twin):
+    dc.check_near_twins(dedup, dedup_twin.hashes)
+
+
+@pytest.mark.parametrize("word", [4, 6])
+def test_dedup_counter_family_spreads(dedup, dedup_twin, word):
+    keys = dc.counter_family(word)
+    r = dedup.run(keys, 2 * len(keys))
+    dc.check_model(keys, r, 2 * len(keys))
+    assert (r.hashes == dedup_twin.run(keys, 2 * len(keys)).hashes).all()
+    assert dc.displacement(keys, r, 2 * len(keys)) <= len(keys)

@@ -67,22 +67,40 @@ def test_random_batch_vs_oracle(gpu_engine, oracle):
     assert 0.5 < want.mean() < 0.75
 
 
-def test_general_key_dedupe(gpu_engine, oracle):
+def _same_home_key(twin, key, word, nslots):
+    """key with another value in one of its words and the same home slot of nslots (key_hash of
+    csrc/key_dedup.h, as the host build computes it)"""
+    home = twin.hashes([key])[0] % nslots
+    w = int.from_bytes(key[4 * word:4 * word + 4], "little")
+    cand = [key[:4 * word] + (w ^ c).to_bytes(4, "little") + key[4 * word + 4:] for c in range(1, 1 << 16)]
+    return next(k for k, h in zip(cand, twin.hashes(cand)) if h % nslots == home)
+
+
+def test_general_key_dedupe(gpu_engine, oracle, hostcheck):
     """General path, distinct-key dedupe (edv_dedup_*): requests share keys;
-    keys that differ only in words the slot hash ignores (bytes 16..19 and
-    24..27) collide in the hash table and must still get their own tables;
-    a non-decodable key repeated across requests rejects all of them."""
+    keys that differ from a signer's in one word (bytes 16..19, bytes 24..27)
+    and were picked to share its home slot collide in the hash table and must
+    still get their own tables; a non-decodable key repeated across requests
+    rejects all of them."""
+    import dedup_cases as dc
+    twin = dc.Dedup(hostcheck, "edv_host_ed")
     rng = np.random.default_rng(11)
     pk, sk = gpu_engine.seed_keypair_batch(rng.integers(0, 256, (5, 32), dtype=np.uint8))
     n = 2500
+    nslots = 2 * n  # one sub-batch (pipeline = 1): edv_dedup_insert_kernel's table
     kidx = rng.integers(0, 5, n).astype(np.uint32)
     msgs = [bytes(rng.integers(0, 256, int(rng.integers(0, 300)), dtype=np.uint8)) for _ in range(n)]
     buf, off = pack_messages(msgs)
     sig = gpu_engine.sign_batch(sk, kidx, buf, off)
     pks = pk[kidx].copy()
     variant = rng.integers(0, 4, n)
-    pks[variant == 1, 16] ^= 0x01  # same slot hash as the true key
-    pks[variant == 2, 25] ^= 0x40  # ditto
+    for v, word in ((1, 4), (2, 6)):
+        near = [_same_home_key(twin, k.tobytes(), word, nslots) for k in pk]
+        homes = [h % nslots for h in twin.hashes([k.tobytes() for k in pk] + near)]
+        assert homes[:5] == homes[5:] and all(a != k.tobytes() for a, k in zip(near, pk))  # the collision happens
+        near = np.frombuffer(b"".join(near), np.uint8).reshape(5, 32)
+        pks[variant == v] = near[kidx[variant == v]]
+    assert gpu_engine.get_options()["pipeline"] == 1
     pks[variant == 3] = pk[kidx[variant == 3]]
     pks[variant == 3, 31] = 0x7F  # y >= p for many keys: usually fails to decode
     pks[variant == 3, :31] = 0xFF
