@@ -441,6 +441,17 @@ int edv_wire_idents(edv_ctx *ctx, uint32_t *uidx, uint32_t *uniq_item, uint64_t 
  * otherwise, with no uidx of this batch (edv_wire_idents not called, or the batch rescanned
  * since), or with n_uniq not the batch's count -- the caller then uses edv_wire_verify. */
 int edv_wire_verify_idents(edv_ctx *ctx, const uint32_t *kid_u, uint64_t n_uniq, uint8_t *accept_bits);
+/* edv_wire_verify for ANY mix of items, with one key per distinct identifier: the verdicts of
+ * edv_wire_verify(key_id[i] = kid_u[uidx[i]], pk32[i] = pk_u[32*uidx[i]..]), bit for bit, an item
+ * with status != 0 (uidx[i] = n_uniq) keeping bit 0.  kid_u[j] = a registered key id,
+ * EDV_WIRE_NO_ID (general path, the key in pk_u[32*j..]; pk_u may be NULL when no identifier uses
+ * it) or EDV_WIRE_SKIP (the identifier's items keep bit 0).  The GPU builds the work list
+ * (csrc/wire_once.h): 4*n_uniq (+ 32*n_uniq) bytes go up, n/8 come back.  once != 0: each
+ * distinct (identifier, signature, message) is verified once and the copies take its verdict.
+ * *n_verified = the lanes the verify kernels ran.  EDV_EINVAL as edv_wire_verify_idents for a
+ * missing batch, uidx or a wrong n_uniq; for a null pointer; for NO_ID without pk_u. */
+int edv_wire_verify_list(edv_ctx *ctx, const uint32_t *kid_u, const uint8_t *pk_u, uint64_t n_uniq,
+                         uint32_t once, uint8_t *accept_bits, uint64_t *n_verified);
 /* DIAGNOSTIC: read the wire batch back -- sig64[n*64], msgs (item i at text_off[i]-text_off[0]),
  * msg_len[n] -- so tests compare bytes, not only verdicts.  Items with status != 0 read as zero
  * length; their sig64 and msgs bytes are unspecified. */

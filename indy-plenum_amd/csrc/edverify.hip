@@ -59,6 +59,7 @@
 #include "verify_core.h"
 #include "node_split_lanes.h"
 #include "wire_idents.h"
+#include "wire_once.h"
 #include "wire_scan.h"
 #include "wire_unwrap.h"
 
@@ -976,6 +977,102 @@ __global__ __launch_bounds__(kBlock) void edv_wire_ident_keys_kernel(uint64_t n,
   keys[i] = u < nu ? kid_u[u] : EDV_WIRE_SKIP;  // (every item has an identifier: checked on the host)
 }
 
+// ---- the wire batch's work list (edverify.h edv_wire_verify_list; the lane code is wire_once.h) ----
+// One lane per item over what the scan and edv_wire_idents left in HBM.  select: grp[i] = the
+// item's group from status, uidx and the nu per-identifier key ids; with `once`, the live items
+// into the table (owner / first, kIdentEmpty beforehand), slot[i] = the item's slot -- kIdentEmpty
+// without `once`, after kWireOnceProbe slots, or for a dead item.  A live item whose message span
+// is not inside the batch's messages is made dead and raises *bad (never read).  flag (after the
+// kernel boundary: first[] is final): per group, the item is a lane of the verify, n + 1 entries,
+// the last one 0, so that their exclusive sums end in the groups' lane counts.  gather: lane
+// rank[i] of the item's group gets its signature, span pair and key.  scatter: the item's bit is
+// its representative's; a wave's 64 items are one word, stored by its first lane.
+static_assert(kOnceNoId == EDV_WIRE_NO_ID && kOnceSkip == EDV_WIRE_SKIP, "wire_once.h names edverify.h's key ids");
+struct WireMsgBytes {  // the serializations as the scan left them; word64 at any byte position
+  const uint8_t* p;
+  __device__ __forceinline__ uint32_t operator[](uint64_t b) const { return p[b]; }
+  __device__ __forceinline__ uint64_t word64(uint64_t b) const {
+    uint64_t v;
+    __builtin_memcpy(&v, p + b, 8);  // (alignment 1: the compiler picks loads that are correct there)
+    return v;
+  }
+};
+
+__global__ __launch_bounds__(kBlock) void edv_wire_once_select_kernel(
+    uint64_t n, const uint8_t* __restrict__ status, const uint32_t* __restrict__ uidx, uint32_t nu,
+    const uint32_t* __restrict__ kid_u, const uint32_t* __restrict__ sigw, const uint64_t* __restrict__ spans,
+    const uint8_t* __restrict__ msg, uint64_t msg_bytes, uint32_t* owner, uint32_t* first, uint32_t cap, uint32_t once,
+    uint32_t* __restrict__ slot, uint8_t* __restrict__ grp, uint32_t* __restrict__ bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t *ms = spans, *me = spans + n;
+  uint32_t g = wo_group(status, uidx, kid_u, nu, i), s = kIdentEmpty;
+  if (g != kOnceDead && !wo_span_ok(ms, me, msg_bytes, i)) {
+    g = kOnceDead;
+    *bad = 1;
+  }
+  if (g != kOnceDead && once)
+    s = wo_insert(sigw, ms, me, WireMsgBytes{msg}, uidx, WireIdentTable{owner, first}, cap, kWireOnceProbe, (uint32_t)i);
+  slot[i] = s;
+  grp[i] = (uint8_t)g;
+}
+
+__global__ __launch_bounds__(kBlock) void edv_wire_once_flag_kernel(uint64_t n, const uint8_t* __restrict__ grp,
+                                                                   const uint32_t* __restrict__ slot,
+                                                                   const uint32_t* __restrict__ first,
+                                                                   uint32_t* __restrict__ flag_k,
+                                                                   uint32_t* __restrict__ flag_g) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  flag_k[i] = i < n ? wo_flag(grp, slot, first, kOnceKeyed, i) : 0u;
+  flag_g[i] = i < n ? wo_flag(grp, slot, first, kOnceGeneral, i) : 0u;
+}
+
+__global__ __launch_bounds__(kBlock) void edv_wire_once_gather_kernel(
+    uint64_t n, const uint8_t* __restrict__ grp, const uint32_t* __restrict__ slot, const uint32_t* __restrict__ first,
+    const uint32_t* __restrict__ rank_k, const uint32_t* __restrict__ rank_g, uint64_t m_k, uint64_t m_g,
+    const uint32_t* __restrict__ uidx, uint32_t nu, const uint32_t* __restrict__ kid_u, const uint32_t* __restrict__ pk_u,
+    const uint32_t* __restrict__ sigw, const uint64_t* __restrict__ spans, uint32_t* __restrict__ sig_k,
+    uint64_t* __restrict__ spans_k, uint32_t* __restrict__ keys_k, uint32_t* __restrict__ sig_g,
+    uint64_t* __restrict__ spans_g, uint32_t* __restrict__ pk_g) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t g = grp[i], u = uidx[i];
+  if (g == kOnceDead || u >= nu || wo_rep(slot, first, i) != (uint32_t)i) return;
+  const uint64_t *ms = spans, *me = spans + n;
+  if (g == kOnceKeyed) {
+    const uint64_t j = rank_k[i];
+    if (j >= m_k) return;  // (never: rank[i] < rank[n] for a flagged item)
+    wo_emit(sigw, ms, me, i, j, m_k, sig_k, spans_k);
+    keys_k[j] = kid_u[u];
+  } else {
+    const uint64_t j = rank_g[i];
+    if (j >= m_g) return;
+    wo_emit(sigw, ms, me, i, j, m_g, sig_g, spans_g);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) pk_g[8 * j + k] = pk_u[8 * (uint64_t)u + k];
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void edv_wire_once_scatter_kernel(
+    uint64_t n, const uint8_t* __restrict__ grp, const uint32_t* __restrict__ slot, const uint32_t* __restrict__ first,
+    const uint32_t* __restrict__ rank_k, const uint32_t* __restrict__ rank_g, uint64_t m_k, uint64_t m_g,
+    const unsigned long long* __restrict__ words_k, const unsigned long long* __restrict__ words_g,
+    unsigned long long* __restrict__ words) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if ((i & ~63ull) >= n) return;  // whole wave past the end (wave-uniform)
+  uint32_t bit = 0;
+  if (i < n) {
+    const uint32_t g = grp[i];
+    const uint32_t r = g != kOnceDead ? wo_rep(slot, first, i) : 0u;
+    // (never out of range: a representative is an item of the same group, ranked below the count)
+    if (g != kOnceDead && r < n && (g == kOnceKeyed ? rank_k[r] < m_k : rank_g[r] < m_g))
+      bit = wo_bit(grp, slot, first, rank_k, rank_g, words_k, words_g, i);
+  }
+  const unsigned long long bits = __ballot(bit != 0);
+  if ((i & 63) == 0) words[i >> 6] = bits;
+}
+
 // ---- key order of the comb (edv_options.key_sort) ------------------------------
 // A counting sort of a sub-batch's key ids: requests of one key become
 // neighbours, so a wave's 64 comb lanes gather from one key's rows (a few
@@ -1837,6 +1934,9 @@ struct edv_ctx {
   // ([n + 1] each) and index (w_uidx, kept for edv_wire_verify_idents until the next scan), the
   // first occurrences, the scan's scratch, a flag word, the per-identifier key ids; pinned staging
   Buf w_itab, w_islot, w_iflag, w_irank, w_uidx, w_uitem, w_itmp, w_ibad, w_ikid, wh_idents, wh_ikid;
+  // edv_wire_verify_list (the table, slots, flags, ranks and scratch are edv_wire_idents', free
+  // once w_uidx is made): per item its group, the general identifiers' keys, pinned staging
+  Buf w_ogrp, w_opk, wh_opk;
   bool wire_uidx_ok = false, wire_all_live = false;
   uint64_t wire_nu = 0;
   std::vector<uint8_t> wire_status;
@@ -3922,6 +4022,105 @@ int edv_wire_verify_idents(edv_ctx* ctx, const uint32_t* kid_u, uint64_t n_uniq,
   return 0;
 }
 
+int edv_wire_verify_list(edv_ctx* ctx, const uint32_t* kid_u, const uint8_t* pk_u, uint64_t n_uniq, uint32_t once,
+                         uint8_t* accept_bits, uint64_t* n_verified) {
+  int r = set_device(ctx);
+  if (r) return r;
+  if (!ctx->wire_ok) return set_err(EDV_EINVAL, "no wire batch (edv_wire_scan first)");
+  if (!ctx->wire_uidx_ok) return set_err(EDV_EINVAL, "no identifier indices for this wire batch (edv_wire_idents first)");
+  if (n_uniq != ctx->wire_nu)
+    return set_err(EDV_EINVAL, "the wire batch holds %llu identifiers", (unsigned long long)ctx->wire_nu);
+  if (!n_verified) return set_err(EDV_EINVAL, "null pointer");
+  *n_verified = 0;
+  const uint64_t n = ctx->wire_n, nu = n_uniq;
+  if (n == 0) return 0;
+  if (!accept_bits || (nu && !kid_u)) return set_err(EDV_EINVAL, "null pointer");
+  uint64_t general = 0;
+  for (uint64_t j = 0; j < nu; ++j) general += (uint64_t)(kid_u[j] == EDV_WIRE_NO_ID);
+  if (general && !pk_u) return set_err(EDV_EINVAL, "null pk_u with EDV_WIRE_NO_ID identifiers");
+  memset(accept_bits, 0, (size_t)((n + 7) / 8));
+  if (nu == 0) return 0;  // (no scanned item)
+  uint64_t cap = 64;
+  while (cap < 2 * n) cap <<= 1;  // (n < 2^32 - 2: the scan's bound)
+  if (cap > 0x80000000ull) return set_err(EDV_EINVAL, "too many items for the table");
+  hipStream_t st = ctx->stream;
+  size_t tmp = 0;
+  HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)(n + 1),
+                                  rocprim::plus<uint32_t>(), st));
+  const uint64_t nwords = div_up(n, 64);
+  if ((r = ensure(ctx->w_itab, 8 * cap)) || (r = ensure(ctx->w_islot, 4 * n)) || (r = ensure(ctx->w_iflag, 8 * (n + 1))) ||
+      (r = ensure(ctx->w_irank, 8 * (n + 1))) || (r = ensure(ctx->w_itmp, tmp)) || (r = ensure(ctx->w_ibad, 16)) ||
+      (r = ensure(ctx->w_ogrp, n)) || (r = ensure(ctx->w_ikid, 4 * nu)) || (r = ensure(ctx->w_opk, 32 * nu)) ||
+      (r = ensure(ctx->w_words, 8 * nwords)) || (r = ensure_pinned(ctx->wh_bits, 8 * nwords)) ||
+      (r = ensure_pinned(ctx->wh_idents, 16 + 8 * n)) || (r = ensure_pinned(ctx->wh_ikid, 4 * nu)) ||
+      (r = ensure_pinned(ctx->wh_opk, 32 * nu)))
+    return r;
+  uint32_t* owner = (uint32_t*)ctx->w_itab.p;
+  uint32_t* first = owner + cap;
+  uint32_t *slot = (uint32_t*)ctx->w_islot.p, *flag_k = (uint32_t*)ctx->w_iflag.p, *flag_g = flag_k + (n + 1);
+  uint32_t *rank_k = (uint32_t*)ctx->w_irank.p, *rank_g = rank_k + (n + 1), *d_bad = (uint32_t*)ctx->w_ibad.p;
+  uint8_t* grp = (uint8_t*)ctx->w_ogrp.p;
+  const uint32_t *d_uidx = (const uint32_t*)ctx->w_uidx.p, *d_kid = (const uint32_t*)ctx->w_ikid.p;
+  const uint32_t* sigw = (const uint32_t*)ctx->w_sig.p;
+  const uint64_t* spans = (const uint64_t*)ctx->w_spans.p;
+  memcpy(ctx->wh_ikid.p, kid_u, 4 * nu);
+  HIP_TRY(hipMemcpyAsync(ctx->w_ikid.p, ctx->wh_ikid.p, 4 * nu, hipMemcpyHostToDevice, st));
+  if (general) {
+    memcpy(ctx->wh_opk.p, pk_u, 32 * nu);
+    HIP_TRY(hipMemcpyAsync(ctx->w_opk.p, ctx->wh_opk.p, 32 * nu, hipMemcpyHostToDevice, st));
+  }
+  if (once) HIP_TRY(hipMemsetAsync(owner, 0xff, 8 * cap, st));
+  HIP_TRY(hipMemsetAsync(d_bad, 0, 4, st));
+  const dim3 grid((uint32_t)div_up(n + 1, kBlock)), block(kBlock);
+  hipLaunchKernelGGL(edv_wire_once_select_kernel, grid, block, 0, st, n, (const uint8_t*)ctx->w_status.p, d_uidx,
+                     (uint32_t)nu, d_kid, sigw, spans, (const uint8_t*)ctx->w_msg.p,
+                     kWirePad + ctx->wire_bytes + kWireTail, owner, first, (uint32_t)cap, once ? 1u : 0u, slot, grp, d_bad);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(edv_wire_once_flag_kernel, grid, block, 0, st, n, (const uint8_t*)grp, (const uint32_t*)slot,
+                     (const uint32_t*)first, flag_k, flag_g);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(rocprim::exclusive_scan(ctx->w_itmp.p, tmp, flag_k, rank_k, 0u, (size_t)(n + 1), rocprim::plus<uint32_t>(), st));
+  HIP_TRY(rocprim::exclusive_scan(ctx->w_itmp.p, tmp, flag_g, rank_g, 0u, (size_t)(n + 1), rocprim::plus<uint32_t>(), st));
+  uint32_t* h = (uint32_t*)ctx->wh_idents.p;  // [0] the keyed lanes, [1] the general lanes, [2] the bad-span flag
+  HIP_TRY(hipMemcpyAsync(h, rank_k + n, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h + 1, rank_g + n, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h + 2, d_bad, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint64_t m_k = h[0], m_g = h[1];
+  if (h[2] || m_k + m_g > n) return set_err(EDV_EINVAL, "a message span outside the batch");
+  if (m_k && ctx->key_count == 0) return set_err(EDV_EINVAL, "no registered keys");
+  if (m_k + m_g == 0) return 0;
+  // both groups' inputs in the subset buffers, the keyed group first: keys (ids, then from a
+  // 64-byte boundary the general keys), signatures, span pairs, result words
+  const uint64_t key_g_at = (4 * m_k + 63) & ~63ull, words_k_n = div_up(m_k, 64), words_g_n = div_up(m_g, 64);
+  if ((r = ensure(ctx->sub_d_in, key_g_at + 32 * m_g)) || (r = ensure(ctx->sub_d_sig, 64 * (m_k + m_g))) ||
+      (r = ensure(ctx->sub_d_spans, 16 * (m_k + m_g))) || (r = ensure(ctx->sub_d_words, 8 * (words_k_n + words_g_n))))
+    return r;
+  uint8_t* keys_k = (uint8_t*)ctx->sub_d_in.p;
+  uint8_t* keys_g = keys_k + key_g_at;
+  uint8_t *sig_k = (uint8_t*)ctx->sub_d_sig.p, *sig_g = sig_k + 64 * m_k;
+  uint64_t *sp_k = (uint64_t*)ctx->sub_d_spans.p, *sp_g = sp_k + 2 * m_k;
+  unsigned long long *words_k = (unsigned long long*)ctx->sub_d_words.p, *words_g = words_k + words_k_n;
+  hipLaunchKernelGGL(edv_wire_once_gather_kernel, grid, block, 0, st, n, (const uint8_t*)grp, (const uint32_t*)slot,
+                     (const uint32_t*)first, (const uint32_t*)rank_k, (const uint32_t*)rank_g, m_k, m_g, d_uidx,
+                     (uint32_t)nu, d_kid, (const uint32_t*)ctx->w_opk.p, sigw, spans, (uint32_t*)sig_k, sp_k,
+                     (uint32_t*)keys_k, (uint32_t*)sig_g, sp_g, (uint32_t*)keys_g);
+  HIP_TRY(hipGetLastError());
+  set_bucketing(ctx, false);
+  if ((r = launch_pipeline(ctx, true, sig_k, keys_k, ctx->w_msg.p, sp_k, sp_k + m_k, m_k, words_k, st))) return r;
+  if ((r = launch_pipeline(ctx, false, sig_g, keys_g, ctx->w_msg.p, sp_g, sp_g + m_g, m_g, words_g, st))) return r;
+  hipLaunchKernelGGL(edv_wire_once_scatter_kernel, dim3((uint32_t)div_up(n, kBlock)), block, 0, st, n,
+                     (const uint8_t*)grp, (const uint32_t*)slot, (const uint32_t*)first, (const uint32_t*)rank_k,
+                     (const uint32_t*)rank_g, m_k, m_g, (const unsigned long long*)words_k,
+                     (const unsigned long long*)words_g, (unsigned long long*)ctx->w_words.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(ctx->wh_bits.p, ctx->w_words.p, 8 * nwords, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  memcpy(accept_bits, ctx->wh_bits.p, (size_t)((n + 7) / 8));
+  *n_verified = m_k + m_g;
+  return 0;
+}
+
 int edv_wire_readback(edv_ctx* ctx, uint8_t* sig64, uint8_t* msgs, uint32_t* msg_len) {
   int r = set_device(ctx);
   if (r) return r;
@@ -4159,7 +4358,7 @@ void edv_destroy(edv_ctx* ctx) {
                           &ctx->w_idr, &ctx->w_off, &ctx->w_keys, &ctx->w_words, &ctx->wh_text, &ctx->wh_off,
                           &ctx->wh_out, &ctx->wh_keys, &ctx->wh_bits, &ctx->w_itab, &ctx->w_islot, &ctx->w_iflag,
                           &ctx->w_irank, &ctx->w_uidx, &ctx->w_uitem, &ctx->w_itmp, &ctx->w_ibad, &ctx->w_ikid,
-                          &ctx->wh_idents, &ctx->wh_ikid, &ctx->w_raw, &ctx->w_esc, &ctx->w_cls, &ctx->wh_esc,
+                          &ctx->wh_idents, &ctx->wh_ikid, &ctx->w_ogrp, &ctx->w_opk, &ctx->wh_opk, &ctx->w_raw, &ctx->w_esc, &ctx->w_cls, &ctx->wh_esc,
                           &ctx->w_itext_in, &ctx->w_itext, &ctx->wh_itext, &ctx->w_ent, &ctx->w_eoff, &ctx->w_everd,
                           &ctx->w_ecnt, &ctx->w_ebytes, &ctx->w_emsg0, &ctx->w_ebody0, &ctx->w_etmp, &ctx->w_mentry,
                           &ctx->w_mat, &ctx->wh_etot, &ctx->wh_eres})

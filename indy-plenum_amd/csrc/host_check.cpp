@@ -729,6 +729,83 @@ int64_t hc_wire_idents(const uint8_t* text, const uint64_t* off_p, uint64_t n, c
 }
 }  // extern "C"
 
+// ---- the wire batch's work list (wire_once.h, the code of edv_wire_once_*_kernel's lanes) on the
+// CPU, every read and write asserted in bounds, for tests/test_wire_once.py and the list double.
+#include "wire_once.h"
+namespace {
+struct CheckedMsg {  // the serializations; word64 at any byte position, wholly inside them
+  const uint8_t* p;
+  uint64_t n;
+  uint8_t operator[](uint64_t i) const {
+    EDV_ASSERT(i < n);
+    return p[i];
+  }
+  uint64_t word64(uint64_t i) const {
+    EDV_ASSERT(i <= n && n - i >= 8);
+    uint64_t v;
+    memcpy(&v, p + i, 8);
+    return v;
+  }
+};
+}  // namespace
+extern "C" {
+// The work list of n items: signatures sig64[64 n] (4-byte aligned), message i =
+// msgs[spans[i] .. spans[n + i]) inside msg_bytes bytes, status[n], uidx[n] (nu for an item without
+// an identifier), kid_u[nu] (a key id, 0xffffffff general, 0xfffffffe skip).  once: the live items
+// are inserted in the order order[0 .. n) (a permutation) into a table of cap slots (a power of
+// two), each passing at most `probe` slots.  rep[n] = the item whose verdict the item takes (itself
+// for a dead one), grp[n] = 0 dead, 1 keyed, 2 general; *give_ups = the live items that found no
+// slot, *longest_run = the longest run of occupied slots (around the end; cap for a full table).
+// Returns the number of lanes (live items that are their own representative); -1 a message span
+// outside msg_bytes (no byte outside is read), -2 cap not a power of two.
+int64_t hc_wire_once(const uint8_t* sig64, const uint8_t* msgs, uint64_t msg_bytes, const uint64_t* spans_p, uint64_t n,
+                     const uint8_t* status_p, const uint32_t* uidx_p, const uint32_t* kid_p, uint64_t nu, uint32_t once,
+                     uint64_t cap, uint32_t probe, const uint32_t* order_p, uint32_t* rep_p, uint8_t* grp_p,
+                     uint64_t* give_ups, uint64_t* longest_run) {
+  if (cap == 0 || (cap & (cap - 1)) || cap > 0x80000000ull) return -2;
+  const CheckedArr<const uint32_t> sigw{(const uint32_t*)sig64, 16 * n}, uidx{uidx_p, n}, kid{kid_p, nu}, order{order_p, n};
+  const CheckedArr<const uint64_t> ms{spans_p, n}, me{spans_p + n, n};
+  const CheckedArr<const uint8_t> status{status_p, n};
+  const CheckedArr<uint32_t> rep{rep_p, n};
+  const CheckedArr<uint8_t> grp{grp_p, n};
+  const CheckedMsg msg{msgs, msg_bytes};
+  std::vector<uint32_t> owner_v((size_t)cap, kIdentEmpty), first_v((size_t)cap, kIdentEmpty), slot_v((size_t)n + 1, kIdentEmpty);
+  const SerialTable tab{{owner_v.data(), cap}, {first_v.data(), cap}};
+  const CheckedArr<uint32_t> slot{slot_v.data(), n};
+  bool bad = false;
+  for (uint64_t i = 0; i < n; ++i) {
+    uint32_t g = wo_group(status, uidx, kid, (uint32_t)nu, i);
+    if (g != kOnceDead && !wo_span_ok(ms, me, msg_bytes, i)) {
+      g = kOnceDead;
+      bad = true;
+    }
+    grp[i] = (uint8_t)g;
+  }
+  if (bad) return -1;
+  uint64_t gave = 0;
+  for (uint64_t k = 0; k < n && once; ++k) {
+    const uint32_t i = order[k];
+    if (grp[i] == kOnceDead) continue;
+    slot[i] = wo_insert(sigw, ms, me, msg, uidx, tab, (uint32_t)cap, probe, i);
+    gave += (uint64_t)(slot[i] == kIdentEmpty);
+  }
+  int64_t lanes = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    rep[i] = wo_rep(slot, tab.first, i);
+    lanes += (int64_t)(wo_flag(grp, slot, tab.first, kOnceKeyed, i) + wo_flag(grp, slot, tab.first, kOnceGeneral, i));
+  }
+  uint64_t run = 0, longest = 0, occupied = 0;
+  for (uint64_t s = 0; s < 2 * cap; ++s) {  // (twice around: a run over the end)
+    run = owner_v[(size_t)(s & (cap - 1))] != kIdentEmpty ? run + 1 : 0;
+    if (run > longest) longest = run;
+  }
+  for (uint64_t s = 0; s < cap; ++s) occupied += (uint64_t)(owner_v[(size_t)s] != kIdentEmpty);
+  if (give_ups) *give_ups = gave;
+  if (longest_run) *longest_run = occupied == cap ? cap : longest;
+  return lanes;
+}
+}  // extern "C"
+
 // ---- the device BATCH split (node_split_lanes.h, the code of edv_node_split_count_kernel's and
 // edv_node_split_emit_kernel's lanes) on the CPU as an emulated wave: 64 lanes one after the other,
 // the same Hillis-Steele composition the shuffles do and the same carry from step to step; every

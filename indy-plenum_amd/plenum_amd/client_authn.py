@@ -343,7 +343,8 @@ class _GpuState:
         self.kid_map_version = None
         self.kid_map_max = 1 << 20
         self.stats = {"batches": 0, "batch_items": 0, "cache_hits": 0, "single_verifies": 0, "keyed_items": 0,
-                      "keys_registered": 0, "prefetched": 0, "wire_items": 0, "wire_host_items": 0}
+                      "keys_registered": 0, "prefetched": 0, "wire_items": 0, "wire_host_items": 0,
+                      "wire_list_batches": 0, "wire_distinct_items": 0}
         self.wire_bytes_per_item = 400.0  # sizes the next wire batch's pinned text buffer
         self.node_wire_bytes_per_entry = 4096.0  # ... and the next node wire batch's
         self.last_wire_breakdown = None  # the last wire batch's phases (ms)
@@ -353,6 +354,12 @@ class _GpuState:
         # a node drain's BATCHes split on the GPU (engine.wire_scan_entries, on an engine with
         # supports_wire_split); EDV_WIRE_SPLIT=0: the host split (_hostpack.gather_node_texts)
         self.wire_split_gpu = os.environ.get("EDV_WIRE_SPLIT", "0") != "0"
+        # a wire batch verified from one key per distinct identifier, whatever its mix of items
+        # (engine.wire_verify_list, on an engine with supports_wire_list): every batch off the
+        # steady state; with EDV_WIRE_ONCE=1 (which implies the list) every batch, each distinct
+        # (identifier, signature, message) verified once
+        self.wire_once = os.environ.get("EDV_WIRE_ONCE", "0") != "0"
+        self.wire_list = self.wire_once or os.environ.get("EDV_WIRE_LIST", "0") != "0"
 
 
 class GpuAuthMixin:
@@ -1730,7 +1737,11 @@ class GpuAuthMixin:
             else:
                 kid_u[j] = i
         steady = not general_u and not status.any() and not cls_u[:nu].any()
-        if on_gpu and steady:
+        # one key per identifier, the work list built on the GPU (edv_wire_verify_list): every batch
+        # off the steady state, and the steady ones too when each distinct request is verified once
+        use_list = (on_gpu and g.wire_list and getattr(eng, "supports_wire_list", False)
+                    and (g.wire_once or not steady))
+        if use_list or (on_gpu and steady):
             key_id = None  # (the GPU gathers the per-item ids from kid_u)
         else:
             # (one native pass: numpy's fancy indexing widens the index array to intp first)
@@ -1740,12 +1751,17 @@ class GpuAuthMixin:
         if general_u:
             pk_u = np.zeros((nu + 1, 32), np.uint8)
             pk_u[general_u] = np.frombuffer(b"".join(ukeys[j] for j in general_u), np.uint8).reshape(-1, 32)
-            pk32 = pk_u[uidx]
+            pk32 = None if use_list else pk_u[uidx]
         if steady:
             # every text scanned, every identifier's key registered (the node's steady state):
             # no per-item class array
             t3 = _perf_counter()
-            ok = eng.wire_verify_idents(kid_u[:nu]) if on_gpu else eng.wire_verify(key_id, None)
+            if use_list:
+                ok, distinct = eng.wire_verify_list(kid_u[:nu], None, True)
+                g.stats["wire_list_batches"] += 1
+                g.stats["wire_distinct_items"] += distinct
+            else:
+                ok = eng.wire_verify_idents(kid_u[:nu]) if on_gpu else eng.wire_verify(key_id, None)
             t4 = _perf_counter()
             g.stats["batches"] += 1
             g.stats["batch_items"] += n
@@ -1759,12 +1775,21 @@ class GpuAuthMixin:
         icls = cls_u[uidx]
         t3 = _perf_counter()
         n_verify = int(np.count_nonzero(icls == 0))
-        ok = eng.wire_verify(key_id, pk32) if n_verify else np.zeros(n, bool)
+        if not n_verify:
+            ok = np.zeros(n, bool)
+        elif use_list:
+            ok, distinct = eng.wire_verify_list(kid_u[:nu], pk_u[:nu] if general_u else None, g.wire_once)
+            g.stats["wire_list_batches"] += 1
+            g.stats["wire_distinct_items"] += distinct
+        else:
+            ok = eng.wire_verify(key_id, pk32)
         t4 = _perf_counter()
         if n_verify:
             g.stats["batches"] += 1
             g.stats["batch_items"] += n_verify
-            g.stats["keyed_items"] += int(np.count_nonzero(key_id < eng.WIRE_SKIP))
+            # (a copy that took its verdict from a representative is a batch item like any other)
+            keyed = (kid_u < eng.WIRE_SKIP)[uidx] if key_id is None else key_id < eng.WIRE_SKIP
+            g.stats["keyed_items"] += int(np.count_nonzero(keyed))
         if general_u:  # general-path keys earn a slot by verified requests
             verified_u = np.bincount(uidx[ok], minlength=nu + 1)
             per_key = {}

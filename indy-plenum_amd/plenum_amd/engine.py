@@ -476,6 +476,29 @@ class EdVerifyEngine:
                                                _ptr(bits) if n else None))
         return unpack_bits(bits, n)
 
+    supports_wire_list = True
+
+    def wire_verify_list(self, kid_u, pk_u=None, once=False):
+        """wire_verify(kid_u[uidx], pk_u[uidx]) for any mix of items, with uidx
+        as wire_idents left it in HBM (edv_wire_verify_list): kid_u uint32[nu]
+        -- per distinct identifier a registered key id, WIRE_NO_ID (its key in
+        pk_u[j], uint8[nu, 32]) or WIRE_SKIP; an item with status != 0 is
+        False.  once: each distinct (identifier, signature, message) is
+        verified once and its copies take the verdict.  Returns (ok bool[n],
+        the number of lanes the verify kernels ran)."""
+        kid_u = np.ascontiguousarray(kid_u, dtype=np.uint32)
+        nu = kid_u.shape[0]
+        if pk_u is not None:
+            pk_u = _u8(pk_u, 32)
+            if pk_u.shape[0] != nu:
+                raise ValueError("shape mismatch: key ids %d, keys %d" % (nu, pk_u.shape[0]))
+        n = getattr(self, "_wire_shape", (0, 0))[0]
+        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
+        m = ctypes.c_uint64(0)
+        check(self._lib.edv_wire_verify_list(self._ctx, _ptr(kid_u) if nu else None, _ptr(pk_u), nu, 1 if once else 0,
+                                             _ptr(bits) if n else None, ctypes.byref(m)))
+        return unpack_bits(bits, n), int(m.value)
+
     def wire_readback(self):
         """DIAGNOSTIC (edv_wire_readback): the wire batch's (sig64 uint8[n, 64],
         msgs uint8[text bytes] -- item i's serialization at text_off[i] -

@@ -158,6 +158,23 @@ def propagate_text(req, sender_client):
     return json.dumps({"op": "PROPAGATE", "request": req, "senderClient": sender_client})
 
 
+def three_phase_text(op, inst_id=0, view_no=0, pp_seq_no=1, pp_time=1_500_000_000, digest="d" * 64,
+                     state_root=None, txn_root=None, bls_sig=None):
+    """A PREPARE or COMMIT as a node serializes it (node_messages.py Prepare /
+    Commit, their schemas' field names).  No signed request inside: the node
+    wire path gives it no result."""
+    if op == "PREPARE":
+        msg = {"op": op, "instId": inst_id, "viewNo": view_no, "ppSeqNo": pp_seq_no, "ppTime": pp_time,
+               "digest": digest, "stateRootHash": state_root, "txnRootHash": txn_root}
+    elif op == "COMMIT":
+        msg = {"op": op, "instId": inst_id, "viewNo": view_no, "ppSeqNo": pp_seq_no}
+        if bls_sig is not None:
+            msg["blsSig"] = bls_sig
+    else:
+        raise ValueError("not a three-phase message: %r" % (op,))
+    return json.dumps(msg)
+
+
 def drain_texts(reqs, n_nodes=25, client_names=None):
     """One drain's rxMsgs of a node in an n-node pool: the clients' REQUESTs
     (client stack) and, from each of the other n - 1 nodes, one BATCH with

@@ -21,7 +21,17 @@ their PROPAGATEs from each of the other pool - 1 nodes), about --n signed reques
   (c) authenticate_wire_batch(the bare client texts, same requests)  the scan's own cost, no unwrap
 with the results asserted equal in every batch; p50 and min-max per path and per phase of (a), (a') and (c).
 
-usage: python tools/wire_probe.py [--n 1000000] [--signers 1000] [--batches 10] [--out FILE] [--idents-ab | --node]
+--node --mixed: the --node drain as a running node sees it -- per group of --members requests and
+per sending node one PREPARE and one COMMIT entry next to the BATCH (nodeloop.three_phase_text), so
+no batch is all scanned requests -- three ways alternating in one process, on both pools:
+  (p) EDV_WIRE_LIST=0                  per-item key ids built on the host, edv_wire_verify
+  (l) EDV_WIRE_LIST=1                  one key per identifier, the work list built on the GPU (edv_wire_verify_list)
+  (o) EDV_WIRE_ONCE=1                  (l), each distinct (identifier, signature, message) verified once
+with the results asserted equal in every batch; p50 and min-max of the batch and of its phases.  Then
+(l) and (o) over the bare client texts (authenticate_wire_batch, no copies: what `once` costs a
+drain it cannot help).
+
+usage: python tools/wire_probe.py [--n 1000000] [--signers 1000] [--batches 10] [--out FILE] [--idents-ab | --node [--mixed]]
        python tools/wire_probe.py --write-corpus FILE        (no GPU: the test corpora, length-prefixed,
        python tools/wire_probe.py --write-node-corpus FILE    for indy-plenum_amd/build/wire_corpus_check [--node])
 """
@@ -192,6 +202,81 @@ def node_probe(eng, args, texts, dicts, idrs, vks):
     return out
 
 
+def mixed_probe(eng, args, texts, dicts, idrs, vks):
+    """Paths (p), (l), (o) over a 4-node and a 25-node pool's mixed drain, then (l), (o) over the bare texts."""
+    from plenum_amd import nodeloop
+    from plenum_amd.client_authn import GpuAuthNr
+    auth = {}
+    for name, (use_list, once) in (("parent", (False, False)), ("list", (True, False)), ("once", (True, True))):
+        a = auth[name] = GpuAuthNr(engine=eng)
+        a._g.wire_split_gpu, a._g.wire_list, a._g.wire_once = False, use_list, once
+        for idr, vk in zip(idrs, vks):
+            a.addIdr(idr, vk)
+        a.keys_settle()
+    phases = ("gather", "scan", "keys", "verify", "results")
+
+    def run(paths, check):
+        for f in paths.values():  # warm-up: buffers grown, kernels loaded
+            f()
+        times = {k: [] for k in paths}
+        breakdown = {k: [] for k in paths}
+        for _ in range(args.batches):
+            res = {}
+            for name, f in paths.items():
+                t0 = time.perf_counter()
+                res[name] = f()
+                times[name].append((time.perf_counter() - t0) * 1e3)
+                breakdown[name].append(dict(auth[name]._g.last_wire_breakdown))
+            first = next(iter(res.values()))
+            assert all(r == first for r in res.values()), "results differ between the paths"
+            check(first)
+            del res, first
+        row = {}
+        for name, ts in times.items():
+            row[name] = {"batch_ms": _spread(ts)}
+            for k in phases:
+                row[name][k + "_ms"] = _spread([b[k] for b in breakdown[name]])
+        return row
+
+    out = {"n": args.n, "signers": args.signers, "batches": args.batches, "members": args.members, "pools": {}}
+    for pool in (4, 25):
+        reqs = min(len(dicts), max(1, args.n // (pool - 1)))
+        entries, n_req = [], 0
+        for g0 in range(0, reqs, args.members):
+            group = range(g0, min(reqs, g0 + args.members))
+            _, node = nodeloop.drain_texts([dicts[i] for i in group], n_nodes=pool)
+            for k, (t, _) in enumerate(node):
+                entries.append(t.encode())
+                entries.append(nodeloop.three_phase_text("PREPARE", pp_seq_no=g0 // args.members + 1).encode())
+                entries.append(nodeloop.three_phase_text("COMMIT", pp_seq_no=g0 // args.members + 1).encode())
+            n_req += len(group) * (pool - 1)
+        stats0 = {k: dict(a.stats) for k, a in auth.items()}
+
+        def check(res, n_req=n_req):
+            flat = [r for per in res for r in per]
+            assert len(flat) == n_req and all(r.__class__ is str for r in flat)
+
+        row = run({k: (lambda a=a: a.authenticate_node_wire_batch(entries)) for k, a in auth.items()}, check)
+        row.update(entries=len(entries), requests=n_req, distinct_requests=reqs, entry_bytes=sum(map(len, entries)))
+        calls = args.batches + 1
+        for k, a in auth.items():
+            assert a.stats["wire_host_items"] == stats0[k]["wire_host_items"], "the GPU left messages to the host"
+            row[k]["list_batches"] = (a.stats["wire_list_batches"] - stats0[k]["wire_list_batches"]) // calls
+            row[k]["verified_lanes"] = (a.stats["wire_distinct_items"] - stats0[k]["wire_distinct_items"]) // calls
+        out["pools"][str(pool)] = row
+        print("pool %d: %s" % (pool, json.dumps(row)), flush=True)
+        del entries
+    bare = {k: (lambda a=auth[k]: a.authenticate_wire_batch(texts)) for k in ("list", "once")}
+
+    def check_bare(res):
+        assert len(res) == len(texts) and all(r.__class__ is str for r in res)
+
+    out["bare"] = run(bare, check_bare)
+    out["bare"]["requests"] = len(texts)
+    print("bare: %s" % json.dumps(out["bare"]), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -203,6 +288,7 @@ def main():
     ap.add_argument("--write-node-corpus", default=None)
     ap.add_argument("--idents-ab", action="store_true")
     ap.add_argument("--node", action="store_true")
+    ap.add_argument("--mixed", action="store_true", help="--node: PREPARE and COMMIT entries in the drain; list / once A/B")
     ap.add_argument("--members", type=int, default=70, help="--node: PROPAGATEs per BATCH")
     args = ap.parse_args()
     if args.write_corpus:
@@ -217,7 +303,8 @@ def main():
     print("built %d requests, %.0f B mean text, in %.1f s" % (
         args.n, sum(len(t) for t in texts[:1000]) / min(args.n, 1000), time.perf_counter() - t0), flush=True)
     if args.idents_ab or args.node:
-        line = json.dumps(node_probe(eng, args, texts, dicts, idrs, vks) if args.node
+        line = json.dumps(mixed_probe(eng, args, texts, dicts, idrs, vks) if args.node and args.mixed
+                          else node_probe(eng, args, texts, dicts, idrs, vks) if args.node
                           else idents_ab(eng, args, texts, idrs, vks))
         print(line, flush=True)
         if args.out:
