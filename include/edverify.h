@@ -452,6 +452,17 @@ int edv_wire_verify_idents(edv_ctx *ctx, const uint32_t *kid_u, uint64_t n_uniq,
  * missing batch, uidx or a wrong n_uniq; for a null pointer; for NO_ID without pk_u. */
 int edv_wire_verify_list(edv_ctx *ctx, const uint32_t *kid_u, const uint8_t *pk_u, uint64_t n_uniq,
                          uint32_t once, uint8_t *accept_bits, uint64_t *n_verified);
+/* Request.digest (plenum/common/request.py:51-52) of the wire batch's items, hashed on the GPU from
+ * the signing bytes the scan left in HBM (edv_wire_digest_kernel, csrc/wire_digest.h): have[i] = 1
+ * and digest32[32*i..] = sha256(serialize_msg_for_signing(signingState)) for an item with status 0
+ * whose top-level keys are all among identifier / reqId / operation / protocolVersion / signature,
+ * with reqId and operation present and protocolVersion absent or not null -- exactly the items
+ * whose signed bytes ARE the signingState bytes; have[i] = 0 and a zero row for every other item
+ * (the caller serializes those itself).  n = the wire batch's item count (after
+ * edv_wire_scan_entries its *n_msgs).  May be called before or after any edv_wire_verify*; reads
+ * the wire batch and writes buffers of its own only.  Pinned memory from edv_host_alloc is DMA'd
+ * into in place.  EDV_EINVAL without a wire batch or for a null pointer. */
+int edv_wire_digests(edv_ctx *ctx, uint8_t *digest32, uint8_t *have);
 /* DIAGNOSTIC: read the wire batch back -- sig64[n*64], msgs (item i at text_off[i]-text_off[0]),
  * msg_len[n] -- so tests compare bytes, not only verdicts.  Items with status != 0 read as zero
  * length; their sig64 and msgs bytes are unspecified. */

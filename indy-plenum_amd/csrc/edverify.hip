@@ -58,6 +58,7 @@
 #include "sig_slot.h"
 #include "verify_core.h"
 #include "node_split_lanes.h"
+#include "wire_digest.h"
 #include "wire_idents.h"
 #include "wire_once.h"
 #include "wire_scan.h"
@@ -1691,6 +1692,52 @@ __global__ __launch_bounds__(kBlock) void edv_sha256_kernel(const uint8_t* __res
   o[1] = make_uint4(d[4], d[5], d[6], d[7]);
 }
 
+// ---- the wire batch's request digests (edverify.h edv_wire_digests; the lane code is wire_digest.h)
+// One lane per item over what the scan left in HBM: a status-0 item whose top level says that its
+// serialization is its signingState's (wd_eligible) has that span of `msgs` hashed; every other
+// item gets have 0 and a zero row.  The lane walks its text front to back through WireChunks: the
+// 16 aligned bytes around the byte asked for, kept in registers until the walk leaves them -- one
+// 16-byte load per 16 bytes of text instead of one load per byte (`text` is the allocation, byte
+// b of the caller's buffer at text[b - base + kWirePad]: the zeroed bytes in front and behind keep
+// every such load inside it; the walk itself is bounded by the item's length).
+struct WireChunks {
+  const uint8_t* p;
+  uint64_t base;
+  uint64_t q = ~0ull;  // the chunk held
+  uint4 v = {0u, 0u, 0u, 0u};
+  __device__ __forceinline__ uint32_t operator[](uint64_t b) {
+    const uint64_t pos = b - base + kWirePad;
+    if ((pos >> 4) != q) {
+      q = pos >> 4;
+      v = *(const uint4*)(p + 16 * q);
+    }
+    const uint32_t k = (uint32_t)(pos >> 2) & 3u;
+    const uint32_t w = k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w;
+    return (w >> (8u * ((uint32_t)pos & 3u))) & 0xffu;
+  }
+};
+
+__global__ __launch_bounds__(kBlock) void edv_wire_digest_kernel(
+    const uint8_t* __restrict__ text, const uint64_t* __restrict__ off, uint64_t base, uint64_t n,
+    const uint8_t* __restrict__ status, const uint8_t* __restrict__ msgs, uint64_t msg_bytes,
+    const uint64_t* __restrict__ spans, uint8_t* __restrict__ dig, uint8_t* __restrict__ have) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t d[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  uint32_t ok = 0;
+  if (status[i] == (uint8_t)kWireOk) {
+    const uint64_t a = off[i], b = off[i + 1];
+    if (b >= a && b - a <= kWireMaxText) ok = wd_eligible(WireChunks{text, base}, a, (uint32_t)(b - a));
+    const uint64_t ms = spans[i], me = spans[n + i];
+    if (ms > me || me > msg_bytes) ok = 0;  // (never: the scan wrote the span inside the item)
+    if (ok) sha256_msg(d, msgs + ms, me - ms);
+  }
+  uint4* o = (uint4*)(dig + 32 * i);
+  o[0] = make_uint4(d[0], d[1], d[2], d[3]);
+  o[1] = make_uint4(d[4], d[5], d[6], d[7]);
+  have[i] = (uint8_t)ok;
+}
+
 // Replica.validatePrepare (plenum/server/replica.py:1289-1291): a PREPARE from
 // the primary of its key's view is rejected (SuspiciousNode) before it reaches
 // Prepares.addVote, so it never counts.  primary[k] = that voter (0xff: none).
@@ -1937,6 +1984,9 @@ struct edv_ctx {
   // edv_wire_verify_list (the table, slots, flags, ranks and scratch are edv_wire_idents', free
   // once w_uidx is made): per item its group, the general identifiers' keys, pinned staging
   Buf w_ogrp, w_opk, wh_opk;
+  // edv_wire_digests: a digest row and a flag per item, their pinned staging; read and written by
+  // nothing else
+  Buf w_dig, w_dhave, wh_dig;
   bool wire_uidx_ok = false, wire_all_live = false;
   uint64_t wire_nu = 0;
   std::vector<uint8_t> wire_status;
@@ -4121,6 +4171,34 @@ int edv_wire_verify_list(edv_ctx* ctx, const uint32_t* kid_u, const uint8_t* pk_
   return 0;
 }
 
+int edv_wire_digests(edv_ctx* ctx, uint8_t* digest32, uint8_t* have) {
+  int r = set_device(ctx);
+  if (r) return r;
+  if (!ctx->wire_ok) return set_err(EDV_EINVAL, "no wire batch (edv_wire_scan first)");
+  if (!digest32 || !have) return set_err(EDV_EINVAL, "null pointer");
+  const uint64_t n = ctx->wire_n;
+  if (n == 0) return 0;
+  if ((r = ensure(ctx->w_dig, 32 * n)) || (r = ensure(ctx->w_dhave, n))) return r;
+  // a caller's pinned arrays take their copies directly
+  const bool dig_pinned = pinned_range(digest32, 32 * n), have_pinned = pinned_range(have, n);
+  if ((!dig_pinned || !have_pinned) && (r = ensure_pinned(ctx->wh_dig, 33 * n))) return r;
+  uint8_t* h_dig = dig_pinned ? digest32 : (uint8_t*)ctx->wh_dig.p;
+  uint8_t* h_have = have_pinned ? have : (uint8_t*)ctx->wh_dig.p + 32 * n;
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(edv_wire_digest_kernel, dim3((uint32_t)div_up(n, kBlock)), dim3(kBlock), 0, st,
+                     (const uint8_t*)ctx->w_text.p, (const uint64_t*)ctx->w_off.p, ctx->wire_base, n,
+                     (const uint8_t*)ctx->w_status.p, (const uint8_t*)ctx->w_msg.p,
+                     kWirePad + ctx->wire_bytes + kWireTail, (const uint64_t*)ctx->w_spans.p, (uint8_t*)ctx->w_dig.p,
+                     (uint8_t*)ctx->w_dhave.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h_dig, ctx->w_dig.p, 32 * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_have, ctx->w_dhave.p, n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (!dig_pinned) memcpy(digest32, h_dig, 32 * n);
+  if (!have_pinned) memcpy(have, h_have, n);
+  return 0;
+}
+
 int edv_wire_readback(edv_ctx* ctx, uint8_t* sig64, uint8_t* msgs, uint32_t* msg_len) {
   int r = set_device(ctx);
   if (r) return r;
@@ -4361,7 +4439,7 @@ void edv_destroy(edv_ctx* ctx) {
                           &ctx->wh_idents, &ctx->wh_ikid, &ctx->w_ogrp, &ctx->w_opk, &ctx->wh_opk, &ctx->w_raw, &ctx->w_esc, &ctx->w_cls, &ctx->wh_esc,
                           &ctx->w_itext_in, &ctx->w_itext, &ctx->wh_itext, &ctx->w_ent, &ctx->w_eoff, &ctx->w_everd,
                           &ctx->w_ecnt, &ctx->w_ebytes, &ctx->w_emsg0, &ctx->w_ebody0, &ctx->w_etmp, &ctx->w_mentry,
-                          &ctx->w_mat, &ctx->wh_etot, &ctx->wh_eres})
+                          &ctx->w_mat, &ctx->wh_etot, &ctx->wh_eres, &ctx->w_dig, &ctx->w_dhave, &ctx->wh_dig})
     free_buf(*b);
   for (int k = 0; k < edv_ctx::kSets; ++k) {
     for (edv_ctx::Buf* b : {&ctx->d_stage_set[k], &ctx->d_spans[k], &ctx->s_sig[k], &ctx->s_key[k], &ctx->s_bits[k],

@@ -806,6 +806,44 @@ int64_t hc_wire_once(const uint8_t* sig64, const uint8_t* msgs, uint64_t msg_byt
 }
 }  // extern "C"
 
+// ---- the wire batch's request digests (wire_digest.h, the code of edv_wire_digest_kernel's lanes)
+// on the CPU, every read of the walk asserted inside the item's text, for tests/test_wire_digest.py
+// and the digest double.
+#include "wire_digest.h"
+extern "C" {
+// wd_eligible over text[at .. at + len) alone (the accessor asserts every read inside it).
+uint32_t hc_wd_eligible(const uint8_t* text, uint64_t at, uint32_t len) {
+  return wd_eligible(CheckedBytes{text, at, at + len}, at, len);
+}
+
+// n texts (item i = text[off[i] .. off[i + 1])) with what hc_wire_scan made of them: status[n] and
+// item i's serialization msgs[off[i] - off[0] ..)[: msg_len[i]].  have[n] and digest32[32 n] as
+// edv_wire_digests returns them: 1 and sha256(serialization) for a status-0 item that wd_eligible
+// accepts, 0 and a zero row for every other item.
+void hc_wire_digests(const uint8_t* text, const uint64_t* off_p, uint64_t n, const uint8_t* status_p,
+                     const uint8_t* msgs, const uint32_t* msg_len_p, uint8_t* digest32, uint8_t* have_p) {
+  const CheckedArr<const uint64_t> off{off_p, n + 1};
+  const CheckedArr<const uint8_t> status{status_p, n};
+  const CheckedArr<const uint32_t> msg_len{msg_len_p, n};
+  const CheckedArr<uint8_t> have{have_p, n}, dig{digest32, 32 * n};
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t a = off[i], len = off[i + 1] - off[i];
+    uint32_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t ok = 0;
+    if (status[i] == 0 && len <= kWireMaxText) ok = wd_eligible(CheckedBytes{text, a, a + len}, a, (uint32_t)len);
+    if (ok) {
+      EDV_ASSERT(msg_len[i] <= len);
+      alignas(16) uint8_t m[kWireMaxText + 16];  // (sha256_msg reads whole aligned 16-byte pieces)
+      memset(m, 0, sizeof m);
+      memcpy(m, msgs + (a - off[0]), msg_len[i]);
+      sha256_msg(d, m, msg_len[i]);
+    }
+    for (int k = 0; k < 32; ++k) dig[32 * i + k] = (uint8_t)(d[k >> 2] >> (8 * (k & 3)));
+    have[i] = (uint8_t)ok;
+  }
+}
+}  // extern "C"
+
 // ---- the device BATCH split (node_split_lanes.h, the code of edv_node_split_count_kernel's and
 // edv_node_split_emit_kernel's lanes) on the CPU as an emulated wave: 64 lanes one after the other,
 // the same Hillis-Steele composition the shuffles do and the same carry from step to step; every

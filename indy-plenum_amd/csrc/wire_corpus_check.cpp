@@ -5,7 +5,11 @@
 // a read or write one byte outside either is reported.  Then the corpus as one wire batch -- the
 // texts back to back in a heap block of exactly their total length -- through the identifier pass
 // (wire_idents.h, the lane code of edv_wire_ident_*_kernel) with a table of 2 n slots and again
-// with one just large enough, whose chains wrap.
+// with one just large enough, whose chains wrap.  Every scanned text also goes through the digest
+// pass's top-level walk (wire_digest.h, the lane code of edv_wire_digest_kernel) in its exact-size
+// block, every prefix of a short one in a block of the prefix's size (a text that ends early must
+// not be walked past its end), and every item of the batch block again, where it must give the
+// same answer.
 //
 // --node: the corpus is rxMsgs entries of a node stack.  Every entry, in a heap block of exactly
 // its length, goes through the BATCH parse (node_split.h); every message that yields -- a member
@@ -37,6 +41,7 @@
 
 #include "node_split.h"
 #include "node_split_wave_host.h"
+#include "wire_digest.h"
 #include "wire_idents.h"
 #include "wire_once.h"
 #include "wire_scan.h"
@@ -359,8 +364,8 @@ int main(int argc, char** argv) {
     fclose(f);
     return r;
   }
-  uint64_t texts = 0, scanned = 0, host = 0, out_bytes = 0;
-  std::vector<uint8_t> all, status;
+  uint64_t texts = 0, scanned = 0, host = 0, out_bytes = 0, eligible = 0, prefixes = 0;
+  std::vector<uint8_t> all, status, elig;
   std::vector<uint64_t> off(1, 0);
   std::vector<uint32_t> span;
   for (;;) {
@@ -396,6 +401,15 @@ int main(int argc, char** argv) {
     } else {
       ++host;
     }
+    const uint32_t el = st == edv::kWireOk ? edv::wd_eligible((const uint8_t*)text, 0, len) : 0;
+    eligible += el;
+    elig.push_back((uint8_t)el);
+    for (uint32_t cut = 0; st == edv::kWireOk && len <= 256 && cut < len; ++cut, ++prefixes) {
+      uint8_t* part = (uint8_t*)malloc(cut ? cut : 1);
+      memcpy(part, text, cut);
+      (void)edv::wd_eligible((const uint8_t*)part, 0, cut);
+      free(part);
+    }
     all.insert(all.end(), text, text + len);
     off.push_back(all.size());
     status.push_back((uint8_t)st);
@@ -415,7 +429,17 @@ int main(int argc, char** argv) {
   uint64_t tight = 1;
   while ((long)tight < nu) tight <<= 1;
   const long nu_tight = idents(batch, off, status, span, tight);
+  uint64_t differ = 0;
+  for (uint64_t i = 0; i < texts; ++i)
+    if (status[i] == 0)
+      differ += edv::wd_eligible((const uint8_t*)batch, off[i], (uint32_t)(off[i + 1] - off[i])) != elig[i];
   free(batch);
+  printf("digest walk: eligible %llu of %llu scanned, %llu prefixes walked\n", (unsigned long long)eligible,
+         (unsigned long long)scanned, (unsigned long long)prefixes);
+  if (differ) {
+    fprintf(stderr, "the digest walk gives %llu items another answer inside the batch\n", (unsigned long long)differ);
+    return 1;
+  }
   printf("identifiers %ld (table of %llu slots) %ld (of %llu)\n", nu, (unsigned long long)cap, nu_tight,
          (unsigned long long)tight);
   if (nu < 0 || nu_tight != nu) {

@@ -75,6 +75,7 @@ SIGNATURES = {
     "edv_wire_idents": (_I, [_P, _P, _P, _P]),
     "edv_wire_verify_idents": (_I, [_P, _P, _U64, _P]),
     "edv_wire_verify_list": (_I, [_P, _P, _P, _U64, _U32, _P, _P]),
+    "edv_wire_digests": (_I, [_P, _P, _P]),
     "edv_wire_readback": (_I, [_P, _P, _P, _P]),
     "edv_seed_keypair_batch": (_I, [_P, _P, _U64, _P, _P]),
     "edv_sign_batch_device": (_I, [_P, _P, _P, _P, _P, _U64, _P, _P]),

@@ -344,7 +344,8 @@ class _GpuState:
         self.kid_map_max = 1 << 20
         self.stats = {"batches": 0, "batch_items": 0, "cache_hits": 0, "single_verifies": 0, "keyed_items": 0,
                       "keys_registered": 0, "prefetched": 0, "wire_items": 0, "wire_host_items": 0,
-                      "wire_list_batches": 0, "wire_distinct_items": 0}
+                      "wire_list_batches": 0, "wire_distinct_items": 0, "wire_digest_gpu": 0,
+                      "wire_digest_host": 0}
         self.wire_bytes_per_item = 400.0  # sizes the next wire batch's pinned text buffer
         self.node_wire_bytes_per_entry = 4096.0  # ... and the next node wire batch's
         self.last_wire_breakdown = None  # the last wire batch's phases (ms)
@@ -1592,7 +1593,7 @@ class GpuAuthMixin:
         return ok
 
     # -- request texts from the wire ------------------------------------------------
-    def authenticate_wire_batch(self, texts):
+    def authenticate_wire_batch(self, texts, digests=False):
         """authenticate_batch for requests still in their wire form: texts is a
         list of bytes, each one JSON text as the node received it (zstack.py
         rxMsgs, before deserializeMsg).  Returns, element-wise, what
@@ -1614,17 +1615,32 @@ class GpuAuthMixin:
 
         The wire path neither consults nor fills the verify-ahead verdict cache
         (it is keyed by sig || ser bytes on the host, which this path never
-        materialises there)."""
+        materialises there).
+
+        digests=True: returns (results, digest uint8[n, 32], have bool[n]).
+        have[i] is True iff results[i] is not an exception, and digest[i] is
+        then Request.digest of that request as bytes (request_digest.py:
+        sha256 of the signingState's signing bytes); every other row is zero.
+        The GPU hashes the signing bytes the scan left in HBM
+        (engine.wire_digests, csrc/wire_digest.h) for the requests whose signed
+        bytes are their signingState's; an accepted request with another
+        top-level key, or one the host decoded, is serialized here and hashed
+        in one engine.sha256_batch call, as is every accepted request on an
+        engine without supports_wire_digests or on a whole-batch fallback."""
         was = gc.isenabled()
         gc.disable()
         try:
             eng = self._engine()
             if (_gather_texts is not None and _wire_idents is not None and self._native_host_steps()
                     and getattr(eng, "supports_wire", False) and texts.__class__ is list):
-                res = self._authenticate_wire(texts, eng)
+                res = self._authenticate_wire(texts, eng, digests)
                 if res is not None:
                     return res
-            return self._wire_decoded(texts, range(len(texts)), [None] * len(texts))
+            results = self._wire_decoded(texts, range(len(texts)), [None] * len(texts))
+            if not digests:
+                return results
+            import json
+            return self._wire_digest_triple(eng, results, None, None, lambda i: json.loads(texts[i]))
         finally:
             if was:
                 gc.enable()
@@ -1646,6 +1662,62 @@ class GpuAuthMixin:
         self._g.stats["wire_host_items"] += len(where)
         return results
 
+    def _wire_digest_triple(self, eng, results, gpu, item, decoded, ok=None, unsure=()):
+        """(results, digest uint8[N, 32], have bool[N]) for the flat results of a wire
+        batch.  gpu: engine.wire_digests()'s (digest, have) over the scanned batch, or
+        None; item[k]: the batch item result k came from, -1 for one the host found (None:
+        result k is item k); decoded(k): the request dict of result k, asked for only where
+        the request was accepted and the GPU holds no digest of it.  ok: the verify's
+        verdict per batch item -- result k is accepted iff ok[item[k]], except the results
+        `unsure` (the host's), which are looked at; None: every result is looked at."""
+        import numpy as np
+        from .request_digest import signing_state
+        from .serialization import serialize_msg_for_signing
+        n = len(results)
+        if item is not None:
+            item = np.asarray(item, np.int64)
+        if ok is None:
+            have = np.fromiter((not isinstance(r, Exception) for r in results), bool, count=n)
+        else:  # (no pass over a million results in Python)
+            have = ok.astype(bool) if item is None else ok[np.maximum(item, 0)] & (item >= 0)
+            for k in unsure:
+                have[k] = not isinstance(results[k], Exception)
+        if gpu is None or not n:
+            digest, on_gpu = np.zeros((n, 32), np.uint8), np.zeros(n, bool)
+        elif item is None:  # the engine's rows as they came, the rejected ones' zeroed
+            digest, on_gpu = gpu[0], have & gpu[1]
+            rejected = gpu[1] & ~have
+            if rejected.any():
+                digest[rejected] = 0
+        else:
+            on_gpu = have & gpu[1][np.maximum(item, 0)] & (item >= 0)
+            digest = np.zeros((n, 32), np.uint8)
+            digest[on_gpu] = gpu[0][item[on_gpu]]
+        todo = np.flatnonzero(have & ~on_gpu).tolist()
+        if todo:
+            sers = [serialize_msg_for_signing(signing_state(decoded(k))) for k in todo]
+            digest[todo] = self._sha256_rows(eng, sers)
+        g = self._g
+        g.stats["wire_digest_gpu"] += int(np.count_nonzero(on_gpu))
+        g.stats["wire_digest_host"] += len(todo)
+        return results, digest, have
+
+    @staticmethod
+    def _sha256_rows(eng, sers):
+        """SHA-256 of every message, uint8[n, 32]: one engine.sha256_batch call (a
+        MultiEngine's first engine takes it); an engine with no hash at all -- a test
+        double -- leaves it to hashlib."""
+        import numpy as np
+        sha = getattr(eng, "sha256_batch", None)
+        if sha is None and getattr(eng, "engines", None):
+            sha = getattr(eng.engines[0], "sha256_batch", None)
+        if sha is None:
+            import hashlib
+            return np.frombuffer(b"".join(hashlib.sha256(s).digest() for s in sers), np.uint8).reshape(-1, 32)
+        off = np.zeros(len(sers) + 1, np.uint64)
+        off[1:] = np.cumsum([len(s) for s in sers])
+        return sha(np.frombuffer(b"".join(sers), np.uint8), off)
+
     def _wire_text_buffer(self, eng, nbytes):
         buf = self._pinned(eng, "wire_text", nbytes)
         if buf is None:
@@ -1654,13 +1726,13 @@ class GpuAuthMixin:
                 buf = self._g.__dict__["wire_text_plain"] = bytearray(int(nbytes * 1.25) + 4096)
         return buf
 
-    def _authenticate_wire(self, texts, eng):
+    def _authenticate_wire(self, texts, eng, digests=False):
         """The wire batch on the GPU; None when texts is not a list of bytes."""
         import numpy as np
         g = self._g
         n = len(texts)
         if n == 0:
-            return []
+            return ([], np.zeros((0, 32), np.uint8), np.zeros(0, bool)) if digests else []
         with _engine_lock(eng):
             t0 = _perf_counter()
             buf = self._wire_text_buffer(eng, int(n * g.wire_bytes_per_item) + 4096)
@@ -1688,10 +1760,14 @@ class GpuAuthMixin:
             else:
                 uidx_b, uniq = _wire_idents(buf, off_b, status, span, g.scan_threads)
                 uidx = np.frombuffer(uidx_b, np.uint32)
-            results, host, t3, t4 = self._wire_verdicts(eng, n, status, uidx, uidx_b, uniq, on_gpu)
+            results, host, t3, t4, ok = self._wire_verdicts(eng, n, status, uidx, uidx_b, uniq, on_gpu)
             g.stats["wire_items"] += n - len(host)
             if host:
                 self._wire_decoded(texts, host, results)
+            if digests:
+                import json
+                gpu = eng.wire_digests() if getattr(eng, "supports_wire_digests", False) else None
+                results = self._wire_digest_triple(eng, results, gpu, None, lambda i: json.loads(texts[i]), ok, host)
             t5 = _perf_counter()
             g.last_wire_breakdown = {"gather": (t1 - t0) * 1e3, "scan": (t2 - t1) * 1e3, "keys": (t3 - t2) * 1e3,
                                      "verify": (t4 - t3) * 1e3, "results": (t5 - t4) * 1e3,
@@ -1701,7 +1777,8 @@ class GpuAuthMixin:
     def _wire_verdicts(self, eng, n, status, uidx, uidx_b, uniq, on_gpu):
         """The scanned wire batch's results: (results[n] -- the identifier, or the
         exception instance; None for the items the host decides --, those items'
-        indices, the times before and after the verify)."""
+        indices, the times before and after the verify, the verify's verdicts bool[n]:
+        True exactly where results[i] is the identifier)."""
         import numpy as np
         g = self._g
         nu = len(uniq)
@@ -1771,7 +1848,7 @@ class GpuAuthMixin:
             results = _results_from(ok.view(np.uint8).tobytes(), uidx_b, uniq)
             for i, e in zip(failed.tolist(), fails):
                 results[i] = e
-            return results, [], t3, t4
+            return results, [], t3, t4, ok
         icls = cls_u[uidx]
         t3 = _perf_counter()
         n_verify = int(np.count_nonzero(icls == 0))
@@ -1804,10 +1881,10 @@ class GpuAuthMixin:
             results[i] = e
         for i in np.flatnonzero(icls == 2).tolist():
             results[i] = self._fresh(ukeys[uidx[i]])
-        return results, np.flatnonzero(icls == 3).tolist(), t3, t4
+        return results, np.flatnonzero(icls == 3).tolist(), t3, t4, ok
 
     # -- node messages from the wire --------------------------------------------------
-    def authenticate_node_wire_batch(self, entries):
+    def authenticate_node_wire_batch(self, entries, digests=False):
         """authenticate_wire_batch for a NODE stack's drain: entries is a list of
         bytes, each one rxMsgs text -- a client request, a PROPAGATE, a BATCH of
         such, or any other node message.  Returns a list of lists: out[e] holds
@@ -1830,7 +1907,11 @@ class GpuAuthMixin:
         called once per distinct identifier of the GPU-handled items, in
         first-occurrence order; the verify-ahead cache is neither read nor
         filled.  An engine without the node wire path (a MultiEngine, a test
-        double) takes the host definition for the whole call."""
+        double) takes the host definition for the whole call.
+
+        digests=True: returns (out, digest uint8[N, 32], have bool[N]), the two
+        arrays over the flattened results in order, as authenticate_wire_batch
+        returns them over its items."""
         was = gc.isenabled()
         gc.disable()
         try:
@@ -1838,30 +1919,38 @@ class GpuAuthMixin:
             if (_gather_node_texts is not None and self._native_host_steps()
                     and getattr(eng, "supports_wire_node", False) and getattr(eng, "supports_wire_idents", False)
                     and entries.__class__ is list):
-                res = self._authenticate_node_wire(entries, eng)
+                res = self._authenticate_node_wire(entries, eng, digests)
                 if res is not None:
                     return res
-            return self._node_wire_decoded(entries)
+            return self._node_wire_decoded(entries, digests)
         finally:
             if was:
                 gc.enable()
 
-    def _node_wire_decoded(self, entries):
+    def _node_wire_decoded(self, entries, digests=False):
         """The host definition: requests_in_drain per entry, one authenticate_batch."""
         from .batching import requests_in_drain
         per_entry = [requests_in_drain([e]) for e in entries]
         flat = [r for reqs in per_entry for r in reqs]
-        res = iter(self.authenticate_batch(flat) if flat else ())
+        flat_res = self.authenticate_batch(flat) if flat else []
+        res = iter(flat_res)
         self._g.stats["wire_host_items"] += len(per_entry)
-        return [[next(res) for _ in reqs] for reqs in per_entry]
+        out = [[next(res) for _ in reqs] for reqs in per_entry]
+        if not digests:
+            return out
+        _, digest, have = self._wire_digest_triple(self._engine(), flat_res, None, None, flat.__getitem__)
+        return out, digest, have
 
-    def _authenticate_node_wire(self, entries, eng):
+    def _authenticate_node_wire(self, entries, eng, digests=False):
         """The node drain on the GPU; None when entries is not a list of bytes."""
         import numpy as np
         g = self._g
         n_e = len(entries)
+
+        def nothing(out):
+            return (out, np.zeros((0, 32), np.uint8), np.zeros(0, bool)) if digests else out
         if n_e == 0:
-            return []
+            return nothing([])
         with _engine_lock(eng):
             t0 = _perf_counter()
             split_gpu = (g.wire_split_gpu and _gather_texts is not None
@@ -1884,7 +1973,7 @@ class GpuAuthMixin:
                 cls, status, span, esc, entry, at, off = eng.wire_scan_entries(np.frombuffer(buf, np.uint8), entry_off)
                 n = len(esc)
                 if n == 0:  # (nothing but empty BATCHes)
-                    return [[] for _ in range(n_e)]
+                    return nothing([[] for _ in range(n_e)])
             else:
                 off = np.frombuffer(got[0], np.uint64)
                 esc = np.frombuffer(got[1], np.uint8)
@@ -1893,7 +1982,7 @@ class GpuAuthMixin:
                 n = len(esc)
                 g.node_wire_bytes_per_entry = max(g.node_wire_bytes_per_entry * 0.5, int(off[-1]) / n_e * 1.1)
                 if n == 0:  # (nothing but empty BATCHes)
-                    return [[] for _ in range(n_e)]
+                    return nothing([[] for _ in range(n_e)])
                 t1 = _perf_counter()
                 cls, status, span = eng.wire_scan_node(np.frombuffer(buf, np.uint8), off, esc)
             t2 = _perf_counter()
@@ -1901,24 +1990,40 @@ class GpuAuthMixin:
             pinned = self._pinned(eng, "wire_uidx", 4 * n)
             uidx, uniq_item = eng.wire_idents() if pinned is None else eng.wire_idents(pinned)
             uniq = [str(b, "ascii") for b in eng.wire_ident_text(uniq_item)]
-            results, host, t3, t4 = self._wire_verdicts(eng, n, status, uidx, uidx.data, uniq, True)
+            results, host, t3, t4, ok = self._wire_verdicts(eng, n, status, uidx, uidx.data, uniq, True)
             none = cls == eng.NODE_NONE
             host = [i for i in host if not none[i]]  # (no result for those, whatever their scan status)
             g.stats["wire_items"] += n - int(np.count_nonzero(none)) - len(host)
             counts = np.bincount(entry[~none], minlength=n_e)
+            # (for the digests) item: per flat result the message it came from, -1 where the host found
+            # it, None where result k is message k; src: the request dicts the host found
+            item, src = None, {}
             if host:
-                self._node_wire_host(entries, buf, off, at, esc, entry, host, results, counts)
-                flat = []
+                found = self._node_wire_host(entries, buf, off, at, esc, entry, host, results, counts)
+                flat, item = [], []
                 for i in np.flatnonzero(~none).tolist():
                     r = results[i]
                     if r.__class__ is list:
+                        if digests:
+                            src.update(zip(range(len(flat), len(flat) + len(r)), found[i]))
                         flat += r
+                        item += [-1] * len(r)
                     else:
                         flat.append(r)
+                        item.append(i)
             elif none.any():
-                flat = [results[i] for i in np.flatnonzero(~none).tolist()]
+                item = np.flatnonzero(~none)
+                flat = [results[i] for i in item.tolist()]
             else:
                 flat = results
+            if digests:
+                def decoded(k):  # a GPU-verified request the GPU did not hash: its message, decoded here
+                    if k in src:
+                        return src[k]
+                    return self._node_message_requests(entries, buf, off, at, esc, entry, k if item is None else item[k])[0]
+                gpu = eng.wire_digests() if getattr(eng, "supports_wire_digests", False) else None
+                unsure = () if item is None else np.flatnonzero(np.asarray(item, np.int64) < 0).tolist()
+                _, digest, have = self._wire_digest_triple(eng, flat, gpu, item, decoded, ok, unsure)
             bounds = np.zeros(n_e + 1, np.int64)
             np.cumsum(counts, out=bounds[1:])
             bounds = bounds.tolist()
@@ -1927,30 +2032,34 @@ class GpuAuthMixin:
             g.last_wire_breakdown = {"gather": (t1 - t0) * 1e3, "scan": (t2 - t1) * 1e3, "keys": (t3 - t2) * 1e3,
                                      "verify": (t4 - t3) * 1e3, "results": (t5 - t4) * 1e3,
                                      "items": n, "host_items": len(host)}
-            return out
+            return (out, digest, have) if digests else out
+
+    @staticmethod
+    def _node_message_requests(entries, buf, off, at, esc, entry, i):
+        """The request dicts inside message i, the host's way: the entry itself, or
+        the BATCH member (its still escaped body lies at buf[at[i]:], off[i + 1] -
+        off[i] bytes) turned back into its text and visited one level down as in
+        its BATCH."""
+        import json
+        from .batching import requests_in_drain
+        if esc[i]:
+            body = bytes(memoryview(buf)[int(at[i]):int(at[i]) + int(off[i + 1]) - int(off[i])])
+            return requests_in_drain([{"op": "BATCH", "messages": [json.loads(b'"' + body + b'"')]}])
+        return requests_in_drain([entries[entry[i]]])
 
     def _node_wire_host(self, entries, buf, off, at, esc, entry, host, results, counts):
         """results[i] = the list of results of message i, for i in host, the host's
-        way: the entry itself, or the BATCH member (its still escaped body lies at
-        buf[at[i]:], off[i + 1] - off[i] bytes) turned back into its text and
-        visited one level down as in its BATCH; one authenticate_batch over all of
-        them.  counts[e] (results per entry) is adjusted to what they yield."""
-        import json
-        from .batching import requests_in_drain
-        text = memoryview(buf)
-        found = []
-        for i in host:
-            if esc[i]:
-                body = bytes(text[int(at[i]):int(at[i]) + int(off[i + 1]) - int(off[i])])
-                found.append(requests_in_drain([{"op": "BATCH", "messages": [json.loads(b'"' + body + b'"')]}]))
-            else:
-                found.append(requests_in_drain([entries[entry[i]]]))
+        way (_node_message_requests); one authenticate_batch over all of them.
+        counts[e] (results per entry) is adjusted to what they yield.  Returns the
+        request dicts found, per message."""
+        found = [self._node_message_requests(entries, buf, off, at, esc, entry, i) for i in host]
         flat = [r for reqs in found for r in reqs]
         res = iter(self.authenticate_batch(flat) if flat else ())
         for i, reqs in zip(host, found):
             results[i] = [next(res) for _ in reqs]
             counts[entry[i]] += len(reqs) - 1
         self._g.stats["wire_host_items"] += len(host)
+        return dict(zip(host, found))
 
     def _authenticate_batch_each(self, msgs, identifiers=None, signatures=None):
         n = len(msgs)
@@ -2220,12 +2329,16 @@ class ReqAuthenticator:
             if hasattr(a, "prefetch"):
                 a.prefetch(reqs)
 
-    def authenticate_wire_batch(self, texts):
+    def authenticate_wire_batch(self, texts, digests=False):
         """The core authenticator's verdicts for a batch of request texts as they
         came off the wire (GpuAuthMixin.authenticate_wire_batch)."""
-        return self.core_authenticator.authenticate_wire_batch(texts)
+        core = self.core_authenticator
+        return core.authenticate_wire_batch(texts, digests=True) if digests else core.authenticate_wire_batch(texts)
 
-    def authenticate_node_wire_batch(self, entries):
+    def authenticate_node_wire_batch(self, entries, digests=False):
         """The core authenticator's results, per entry, for a node stack's drain as
         it came off the wire (GpuAuthMixin.authenticate_node_wire_batch)."""
-        return self.core_authenticator.authenticate_node_wire_batch(entries)
+        core = self.core_authenticator
+        if digests:
+            return core.authenticate_node_wire_batch(entries, digests=True)
+        return core.authenticate_node_wire_batch(entries)

@@ -499,6 +499,26 @@ class EdVerifyEngine:
                                              _ptr(bits) if n else None, ctypes.byref(m)))
         return unpack_bits(bits, n), int(m.value)
 
+    supports_wire_digests = True
+
+    def wire_digests(self, out=None):
+        """Request.digest of the wire batch's items, hashed on the GPU from the
+        signing bytes the scan left in HBM (edv_wire_digests): (digest uint8[n,
+        32], have bool[n]).  have[i] is True for a scanned item whose signed
+        bytes are its signingState's (top-level keys among identifier / reqId /
+        operation / protocolVersion / signature, reqId and operation present,
+        protocolVersion not null); every other row is zero.  Before or after
+        any wire_verify*.  out: a writable buffer of 33 n bytes or more that
+        both arrays become views of (host_alloc memory is DMA'd into in place)."""
+        n = getattr(self, "_wire_shape", (0, 0))[0]
+        if out is None or n == 0:  # (an empty batch still passes pointers: the call checks for the batch)
+            out = np.zeros(33 * max(n, 1), np.uint8)
+        dig = np.frombuffer(out, np.uint8, count=32 * n).reshape(n, 32)
+        have = np.frombuffer(out, np.uint8, count=n, offset=32 * n)
+        base = np.frombuffer(out, np.uint8, count=1)
+        check(self._lib.edv_wire_digests(self._ctx, _ptr(dig if n else base), _ptr(have if n else base)))
+        return dig, have.view(bool)
+
     def wire_readback(self):
         """DIAGNOSTIC (edv_wire_readback): the wire batch's (sig64 uint8[n, 64],
         msgs uint8[text bytes] -- item i's serialization at text_off[i] -

@@ -31,7 +31,16 @@ with the results asserted equal in every batch; p50 and min-max of the batch and
 (l) and (o) over the bare client texts (authenticate_wire_batch, no copies: what `once` costs a
 drain it cannot help).
 
-usage: python tools/wire_probe.py [--n 1000000] [--signers 1000] [--batches 10] [--out FILE] [--idents-ab | --node [--mixed]]
+--digests: path (a) with and without the request digests, and what a caller pays for them today,
+alternating in one process:
+  (plain)   authenticate_wire_batch(texts)                                    no digests
+  (digests) authenticate_wire_batch(texts, digests=True)                      hashed on the GPU from the scan's bytes
+  (today)   (plain), then json.loads of every accepted text + request_digests(dicts, engine)
+with every digest asserted equal between the last two in every batch; p50 and min-max per leg and of
+each leg's added time over (plain) in the same round.
+
+usage: python tools/wire_probe.py [--n 1000000] [--signers 1000] [--batches 10] [--out FILE]
+                                  [--idents-ab | --digests | --node [--mixed]]
        python tools/wire_probe.py --write-corpus FILE        (no GPU: the test corpora, length-prefixed,
        python tools/wire_probe.py --write-node-corpus FILE    for indy-plenum_amd/build/wire_corpus_check [--node])
 """
@@ -136,6 +145,52 @@ def idents_ab(eng, args, texts, idrs, vks):
 
 def _spread(ts):
     return {"p50": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}
+
+
+def digests_probe(eng, args, texts, idrs, vks):
+    """Path (a) without digests, with them, and with them the way a caller gets them today."""
+    import numpy as np
+    from plenum_amd.client_authn import GpuAuthNr
+    from plenum_amd.request_digest import request_digests
+    a = GpuAuthNr(engine=eng)
+    for idr, vk in zip(idrs, vks):
+        a.addIdr(idr, vk)
+    a.keys_settle()
+
+    def today():
+        res = a.authenticate_wire_batch(texts)
+        hexes = request_digests([json.loads(t) for t, r in zip(texts, res) if r.__class__ is str], eng)
+        return res, hexes
+
+    legs = {"plain": lambda: a.authenticate_wire_batch(texts),
+            "digests": lambda: a.authenticate_wire_batch(texts, digests=True),
+            "today": today}
+    for f in legs.values():  # warm-up: buffers grown, kernels loaded
+        f()
+    print("warm", flush=True)
+    times = {k: [] for k in legs}
+    for b in range(args.batches):
+        res = {}
+        for name, f in legs.items():
+            t0 = time.perf_counter()
+            res[name] = f()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+        results, digest, have = res["digests"]
+        assert results == res["plain"] == res["today"][0], "verdicts differ between the legs"
+        assert have.all() and all(r.__class__ is str for r in results), "a request of the all-valid batch failed"
+        want = np.frombuffer(bytes.fromhex("".join(res["today"][1])), np.uint8).reshape(-1, 32)
+        assert (digest == want).all(), "digests differ between the GPU's and request_digests"
+        del res, results, digest, have, want
+        print("batch %d: %s" % (b, {k: round(v[-1], 1) for k, v in times.items()}), flush=True)
+    st = a.stats
+    assert st["wire_host_items"] == 0 and st["wire_digest_host"] == 0, "items were left to the host"
+    out = {"n": args.n, "signers": args.signers, "batches": args.batches,
+           "mean_text_bytes": sum(map(len, texts)) / args.n, "wire_digest_gpu": st["wire_digest_gpu"]}
+    for name, ts in times.items():
+        out[name + "_ms"] = _spread(ts)
+    for name in ("digests", "today"):
+        out[name + "_added_ms"] = _spread([t - p for t, p in zip(times[name], times["plain"])])
+    return out
 
 
 def node_probe(eng, args, texts, dicts, idrs, vks):
@@ -287,6 +342,7 @@ def main():
     ap.add_argument("--write-corpus", default=None)
     ap.add_argument("--write-node-corpus", default=None)
     ap.add_argument("--idents-ab", action="store_true")
+    ap.add_argument("--digests", action="store_true")
     ap.add_argument("--node", action="store_true")
     ap.add_argument("--mixed", action="store_true", help="--node: PREPARE and COMMIT entries in the drain; list / once A/B")
     ap.add_argument("--members", type=int, default=70, help="--node: PROPAGATEs per BATCH")
@@ -302,9 +358,10 @@ def main():
     texts, dicts, idrs, vks = build(eng, args.n // 3 if args.node else args.n, args.signers, args.alias_len)
     print("built %d requests, %.0f B mean text, in %.1f s" % (
         args.n, sum(len(t) for t in texts[:1000]) / min(args.n, 1000), time.perf_counter() - t0), flush=True)
-    if args.idents_ab or args.node:
+    if args.idents_ab or args.node or args.digests:
         line = json.dumps(mixed_probe(eng, args, texts, dicts, idrs, vks) if args.node and args.mixed
                           else node_probe(eng, args, texts, dicts, idrs, vks) if args.node
+                          else digests_probe(eng, args, texts, idrs, vks) if args.digests
                           else idents_ab(eng, args, texts, idrs, vks))
         print(line, flush=True)
         if args.out:
